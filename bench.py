@@ -27,6 +27,15 @@ one histogram all-reduce per view (bench_c4band.py, strong scaling).  ``--config
 runs its own stream of views (weak scaling, no data-path collective); value = all ranks' points /
 max-over-ranks time.
 
+A plain run does what the headline figure needs and no more: render and upload the views, one
+counting pass over the pool, settle, warmup, the K timed steps, the result line.  ``--full`` adds
+everything else the benchmark measures or checks: the CPU baseline (``cpu_baseline``), the
+verification of the last timed batch against the plain batch path and the oracle (``verify``), and
+the per-view traffic models that decode every pool view again (``roofline.mask_first``,
+``roofline.traffic_model``).  ``--dump-outputs DIR`` writes what the last timed step computed (the
+clouds a caller of the batch path receives) as ``DIR/<name>.npy``; the inputs are seeded, so two
+builds run with the same arguments can be compared array for array (N > 1: rank 0's clouds alone).
+
 Prints ONE JSON line on stdout (rank 0).  Diagnostics go to stderr.
 """
 from __future__ import annotations
@@ -342,6 +351,58 @@ def read_model(frames, cfg, H, W, dev, carried: bool = True, texture: bool = Tru
     return out
 
 
+DUMP_MAX_BYTES = 48 << 20        # --dump-outputs: bound of the sampled point arrays ...
+DUMP_LIMIT_BYTES = 64_000_000    # ... and of everything one dump writes
+
+
+def dump_outputs(dirname: str, clouds) -> dict:
+    """``--dump-outputs``: what the last timed step computed -- the clouds of its views, as a caller
+    of the batch path receives them -- as ``<name>.npy`` files under ``dirname``:
+
+    ``counts``   float64 [views]      points of each view;
+    ``xyz_sum``  float64 [views, 3]   per-view sums of X, Y, Z over ALL its points (fp64 on device);
+    ``bgr_sum``  float64 [views, 3]   the same of the colours;
+    ``rows``     float64 [n]          the rows of the views' concatenated clouds that ``xyz`` / ``bgr``
+                                      hold: all of them, or, when the clouds exceed
+                                      ``DUMP_MAX_BYTES``, a sorted stratified sample drawn with a
+                                      fixed seed (one row from each of n equal runs of rows);
+    ``xyz``      [n, 3]               those rows' XYZ in the cloud's own precision (float32 | float64);
+    ``bgr``      float32 [n, 3]       those rows' colours.
+
+    The cloud's row order is deterministic (ordered compaction), so equal builds write equal files.
+    Everything written stays within ``DUMP_LIMIT_BYTES`` (asserted).  With ``--gpus N > 1`` rank 0
+    alone dumps -- its own last batch; the other ranks' clouds are not written."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    ns = [int(c.count.item()) for c in clouds]
+    parts = [(c.xyz[:n], c.bgr[:n]) for c, n in zip(clouds, ns)]
+    counts = np.array(ns, dtype=np.float64)
+    xyz = torch.cat([x for x, _ in parts])
+    bgr = torch.cat([b for _, b in parts])
+    total = sum(ns)
+    per_row = 3 * xyz.element_size() + 3 * 4 + 8         # xyz + bgr + rows
+    keep = DUMP_MAX_BYTES // per_row
+    rows = np.arange(total, dtype=np.int64)
+    if total > keep:                 # O(keep) on the host: no permutation of all the rows
+        edges = np.arange(keep + 1, dtype=np.int64) * total // keep
+        lo, width = edges[:-1], np.diff(edges)           # width >= 1 since total > keep
+        rows = lo + np.minimum((np.random.default_rng(20240607).random(keep) * width).astype(np.int64), width - 1)
+    idx = torch.from_numpy(rows).to(xyz.device)
+    arrays = {"counts": counts,
+              "xyz_sum": np.stack([x.double().sum(0).cpu().numpy() for x, _ in parts]),
+              "bgr_sum": np.stack([b.double().sum(0).cpu().numpy() for _, b in parts]),
+              "rows": rows.astype(np.float64),
+              "xyz": xyz[idx].cpu().numpy(),
+              "bgr": bgr[idx].float().cpu().numpy()}
+    nbytes = int(sum(a.nbytes for a in arrays.values()))
+    assert nbytes <= DUMP_LIMIT_BYTES, f"dump of {nbytes} bytes exceeds {DUMP_LIMIT_BYTES}"
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {"dir": dirname, "views": len(parts), "points": total, "rows": int(len(rows)),
+            "bytes": nbytes}
+
+
 RESULT_OUT = sys.stdout          # main() points it at the original stdout
 
 
@@ -392,7 +453,9 @@ def spawn_ranks(n: int, argv, script: str | None = None) -> int:
     return rc
 
 
-def main():
+def parse_args(argv=None):
+    """The command line, with what ``--full`` gates resolved: after it ``args.no_cpu_baseline`` and
+    ``args.no_verify`` say whether those parts run, and ``args.full`` whether the traffic models do."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100, help="timed steps (one fused batch launch each)")
@@ -423,7 +486,24 @@ def main():
     ap.add_argument("--cpu-baseline-only", action="store_true",
                     help="print the JSON line with the CPU baseline alone (no GPU is touched)")
     ap.add_argument("--no-verify", action="store_true")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the CPU baseline, the "
+                         "verification against the plain batch path and the oracle, the per-view traffic models "
+                         "(--no-cpu-baseline / --no-verify leave one of them out again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the clouds of the last timed step to DIR/<name>.npy "
+                         "(dump_outputs; e.g. bench_outputs/, which git ignores); with --gpus N > 1 rank 0 "
+                         "alone writes, its own last batch")
+    args = ap.parse_args(argv)
+    if args.cpu_baseline_only:
+        args.full = True
+    if not args.full:                    # a plain run: nothing beside the headline figure
+        args.no_cpu_baseline = args.no_verify = True
+    return args
+
+
+def main():
+    args = parse_args()
     mode = launch_mode(args.gpus, os.environ)
     if mode == "spawn":
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -440,6 +520,8 @@ def main():
     args.result_out = RESULT_OUT         # (bench_c3 imports this file as module "bench")
     if args.gray_texture and args.config in ("c3", "c5job", "c4band"):
         raise SystemExit("--gray-texture applies to the single-view configs (c2, c4, c5)")
+    if args.dump_outputs and args.config in ("c3", "c5job", "c4band"):
+        raise SystemExit("--dump-outputs applies to the batch-stream configs (c1, c2, c4, c5)")
     if args.config == "c3":
         import bench_c3
         return bench_c3.main(args, wl)
@@ -521,9 +603,12 @@ def main():
         s_main.synchronize()
         pts += [int(clouds[0][k].count.item()) for k in range(B)]
     pts = pts[:P]
-    seg_frames = [mask_first_segments(dframes[v], cfg, H, W, dev) for v in range(P)]
-    models = [read_model(dframes[v], cfg, H, W, dev, carried=args.pipeline in ("fused", "fused2"),
-                         texture=not args.gray_texture) for v in range(P)]
+    # the traffic models decode every pool view again through the maps path: --full only
+    seg_frames = models = None
+    if args.full:
+        seg_frames = [mask_first_segments(dframes[v], cfg, H, W, dev) for v in range(P)]
+        models = [read_model(dframes[v], cfg, H, W, dev, carried=args.pipeline in ("fused", "fused2"),
+                             texture=not args.gray_texture) for v in range(P)]
 
     K, Wm = args.steps, args.warmup
     # the whole run as ONE batch stream: warmup + timed + 2 look-ahead batches whose thresholds
@@ -550,7 +635,8 @@ def main():
     # the mask-first decode's own (white + black of every pixel, each pattern frame's 64-byte
     # segments that hold a valid pixel, 18 B per point)
     wb_b = 2 * H * W
-    bytes_alg = sum(wb_b + 64 * seg_frames[v] + out_b * pts[v] for b in range(Wm, Wm + K) for v in pool_views(b))
+    bytes_alg = (sum(wb_b + 64 * seg_frames[v] + out_b * pts[v] for b in range(Wm, Wm + K) for v in pool_views(b))
+                 if args.full else 0)
     bytes_dense = sum(frame_b + out_b * pts[v] for b in range(Wm, Wm + K) for v in pool_views(b))
 
     def run_range(lo, hi, events=None):
@@ -601,6 +687,15 @@ def main():
     kern_ms = sum(a.elapsed_time(b) for a, b in ev)
     helper_runs = sum(int(np.frombuffer(beng.header(s, k)[3084:3088].cpu().numpy().tobytes(), np.uint32)[0] & 2 != 0)
                       for s in range(NSL) for k in range(B))
+
+    # ---- the last timed batch's clouds, as the timed launches left them (rank 0's)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        torch.cuda.synchronize()
+        dumped = dict(dump_outputs(args.dump_outputs, clouds[(Wm + K - 1) % NSL]), rank=0, ranks_not_dumped=world - 1)
+        log(f"[rank 0] dumped outputs: {dumped}")
+    elif args.dump_outputs:
+        log(f"[rank {rank}] --dump-outputs: rank 0 alone writes its clouds; this rank's are not dumped")
 
     # ---- verification, outside the timed region: the last timed batch's clouds (nothing wrote
     # its slot after it) against the plain batch path (bitwise) and one view against the oracle
@@ -662,21 +757,29 @@ def main():
         pmc_name = "pmc_main_kernel.json" if pkey == "c2" else f"pmc_main_kernel_{pkey}.json"
         traffic_view = pmc["hbm_bytes_per_view"] if pmc else None
         n_pts_mean = float(np.mean(pts))
-        model = {k: round(float(np.mean([m[k] for m in models]))) for k in models[0]}
-        xyz_b = 24 if f64 else 12
-        model["writes"] = round((xyz_b + 3) * n_pts_mean + 1024 * ((H * W + 4095) // 4096))   # cloud + Otsu partials
-        model["total_with_writes"] = model["total"] + model["writes"]
-        traffic_model = {"per_view": model,
-                         "what": "bytes the fused launch must move per view (pool average) at the 128-B read "
-                                 "request size the PMC counters show: white + black, pattern-frame lines holding a "
-                                 "valid pixel, texture lines of valid lanes, the carried batch's white + black; "
-                                 f"writes {xyz_b + 3} B per point ({xyz_b} B XYZ + 3 B BGR) + 1 KB of Otsu partials "
-                                 "per tile"}
-        if pmc:
-            traffic_model["measured_per_view"] = {"reads": pmc.get("fetch_bytes_per_view"),
-                                                  "writes": pmc.get("write_bytes_per_view"),
-                                                  "source": pmc.get("tag")}
-            traffic_model["measured_over_model"] = round(traffic_view / model["total_with_writes"], 4)
+        traffic_model = mask_first = None            # --full: they take decode passes of their own
+        if args.full:
+            model = {k: round(float(np.mean([m[k] for m in models]))) for k in models[0]}
+            xyz_b = 24 if f64 else 12
+            model["writes"] = round((xyz_b + 3) * n_pts_mean + 1024 * ((H * W + 4095) // 4096))   # cloud + Otsu partials
+            model["total_with_writes"] = model["total"] + model["writes"]
+            traffic_model = {"per_view": model,
+                             "what": "bytes the fused launch must move per view (pool average) at the 128-B read "
+                                     "request size the PMC counters show: white + black, pattern-frame lines holding "
+                                     "a valid pixel, texture lines of valid lanes, the carried batch's white + black; "
+                                     f"writes {xyz_b + 3} B per point ({xyz_b} B XYZ + 3 B BGR) + 1 KB of Otsu "
+                                     "partials per tile"}
+            if pmc:
+                traffic_model["measured_per_view"] = {"reads": pmc.get("fetch_bytes_per_view"),
+                                                      "writes": pmc.get("write_bytes_per_view"),
+                                                      "source": pmc.get("tag")}
+                traffic_model["measured_over_model"] = round(traffic_view / model["total_with_writes"], 4)
+            # the kernel reads a pattern frame only where a lane holds a valid pixel (SLG_MASK_FIRST),
+            # so it moves fewer bytes than SURVEY's figure: the same time over the bytes it needs
+            mask_first = {"alg_bytes_per_launch": round(bytes_sum / launches),
+                          "achieved": round(mf_achieved, 1), "frac": round(mf_achieved / HBM_PEAK_GBS, 4),
+                          "what": "white + black of every pixel, each pattern frame's 64-B segments that hold "
+                                  f"a valid pixel, {out_b} B per point"}
         roof = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": round(achieved / HBM_PEAK_GBS, 4),
                 # committed PMC bytes (profiles/pmc_main_kernel*.json) are per view of this config
@@ -701,12 +804,7 @@ def main():
                               f"(3 B texture read, {24 if f64 else 12} B XYZ, 3 B BGR written)" if not args.gray_texture else
                               f"SURVEY 8(d) without the texture read: (2 + 2(nc+nr)) B per pixel + {out_b} B per point "
                               f"({24 if f64 else 12} B XYZ, 3 B BGR written; a gray capture's colour is its white frame)"),
-                # the kernel reads a pattern frame only where a lane holds a valid pixel (SLG_MASK_FIRST),
-                # so it moves fewer bytes than SURVEY's figure: the same time over the bytes it needs
-                "mask_first": {"alg_bytes_per_launch": round(bytes_sum / launches),
-                               "achieved": round(mf_achieved, 1), "frac": round(mf_achieved / HBM_PEAK_GBS, 4),
-                               "what": "white + black of every pixel, each pattern frame's 64-B segments that hold "
-                                       f"a valid pixel, {out_b} B per point"}}
+                "mask_first": mask_first}
         out = {
             "metric": METRIC,
             # a run whose clouds failed verification (any rank) measured nothing valid: no value,
@@ -738,8 +836,10 @@ def main():
                        "decode": "u8 compares, int32 codes; triangulation f64",
                        "parallelism": f"view-sharded x{world}"},
             "roofline": roof,
+            "full": bool(args.full),
             "cpu_baseline": cpu,
             "verify": verify,
+            "dump_outputs": dumped,
         }
         print(json.dumps(out), file=RESULT_OUT, flush=True)
     if world > 1:

@@ -14,6 +14,7 @@
 #   bench            python bench.py (driver defaults)                  -> bench.json / .err
 #   bench=<name>=<args>   python bench.py <args> (commas -> spaces)     -> bench_<name>.json / .err
 #                    e.g. bench=c4=--config,c4   bench=2r=--gpus,2 (with SLG_BENCH_* exported)
+#                    bench=full=--full adds the CPU baseline, the verification and the traffic models
 #   prof             kernel trace + FETCH/WRITE PMC passes (tools/gpu_profile.sh) -> <tag>/prof/
 #   prof=<name>=<args>   the same for bench.py <args> (commas -> spaces)  -> <tag>/prof_<name>/
 #   sq               SQ counter passes (tools/pmc_main.sh)              -> <tag>/sq/
