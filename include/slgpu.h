@@ -409,6 +409,45 @@ int32_t slg_gather_destroy(slg_gather_comm *comm);
 int32_t slg_gatherv_plan(int32_t n_ranks, int32_t rank, int32_t root, int64_t send_bytes,
                          const int64_t *recv_bytes, int64_t *offsets, int32_t *recv_from);
 
+/* ---- Point-cloud cleanup on the device (csrc/cloud_filter.hip): the two deterministic
+ * neighbour filters of the reference's cleanup tab, on a packed DEVICE cloud (xyz float64 [n][3]),
+ * so a reconstructed view is cleaned without leaving HBM.
+ *   slg_radius_outlier      <- ProcessingLogic.remove_radius_outlier (server/processing.py:430-448)
+ *   slg_statistical_outlier <- ProcessingLogic.remove_outliers (server/processing.py:367-388,620)
+ *   slg_cloud_select        <- the select_by_index that follows either (ascending indices)
+ * Semantics (Open3D's RemoveRadiusOutliers / RemoveStatisticalOutliers as published, restated;
+ * parity with an installed Open3D is unpinned), all in fp64 with d2 = (dx*dx + dy*dy) + dz*dz:
+ *   radius:      counts[i] = #{j : d2(i, j) < radius*radius} (i included, strict);
+ *                keep[i] = counts[i] > nb_points.
+ *   statistical: avg[i] = (sum of sqrt of the min(k, n) smallest d2(i, j), i included, ascending)
+ *                / min(k, n);  mean = (sum of avg > 0) / n;  std = sqrt(sum over avg > 0 of
+ *                (avg - mean)^2 / (n - 1));  thr = mean + std_ratio * std;
+ *                keep[i] = avg[i] > 0 && avg[i] < thr.  The two sums are fixed trees over the input
+ *                order (no atomics): the same input gives the same bits.  k <= 64
+ *                (SLG_ERR_UNSUPPORTED above).
+ * `ws` is DEVICE scratch of slg_filter_ws_bytes(n, k) bytes (k = 0 when only the radius filter
+ * and the select use it), 8-byte aligned, not initialised by the caller.  keep_out is uint8 [n]
+ * in input order; counts_out (int32 [n]) and avg_out (float64 [n]) may be NULL; stats_out is
+ * float64 [3] = {mean, std, thr} or NULL.  Asynchronous on `stream`, no host synchronisation.
+ * Afterwards the int32 at the front of ws is 0, or SLG_FILTER_BAD_* bits: a coordinate is NaN or
+ * infinite, or the cloud spans 2^21 or more cells of `radius` on an axis; the outputs are then
+ * unspecified (nothing faults), as with slg_ply_format's `bad`.  After slg_statistical_outlier
+ * the int32 at byte 8 of ws is the number of points whose neighbour search left the grid walk
+ * (isolated points) for the whole-cloud kernel.
+ * slg_cloud_select packs the points with keep != 0, in input order, into out (xyz float64, bgr;
+ * bgr / out->bgr may be NULL; *out->count = points written, at most out->capacity) and their
+ * input indices into index_out (int64 [n] or NULL).  It uses ws but leaves the status word. */
+#define SLG_FILTER_BAD_NONFINITE 1
+#define SLG_FILTER_BAD_EXTENT 2
+int64_t slg_filter_ws_bytes(int64_t n, int32_t k);
+int32_t slg_radius_outlier(const double *xyz, int64_t n, double radius, int32_t nb_points, void *ws,
+                           int64_t ws_bytes, uint8_t *keep_out, int32_t *counts_out, void *stream);
+int32_t slg_statistical_outlier(const double *xyz, int64_t n, int32_t nb_neighbors, double std_ratio,
+                                void *ws, int64_t ws_bytes, uint8_t *keep_out, double *avg_out,
+                                double *stats_out, void *stream);
+int32_t slg_cloud_select(const double *xyz, const uint8_t *bgr, int64_t n, const uint8_t *keep,
+                         const slg_cloud *out, int64_t *index_out, void *ws, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

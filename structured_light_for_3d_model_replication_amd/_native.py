@@ -145,7 +145,12 @@ EXPORTS = {
     "slg_gather_destroy": (c_i32, [c_vp]),
     "slg_gatherv_plan": (c_i32, [c_i32, c_i32, c_i32, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
                                  ctypes.POINTER(c_i32)]),
+    "slg_filter_ws_bytes": (c_i64, [c_i64, c_i32]),
+    "slg_radius_outlier": (c_i32, [c_vp, c_i64, c_dbl, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "slg_statistical_outlier": (c_i32, [c_vp, c_i64, c_i32, c_dbl, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "slg_cloud_select": (c_i32, [c_vp, c_vp, c_i64, c_vp, ctypes.POINTER(Cloud), c_vp, c_vp, c_vp]),
 }
+FILTER_BAD_NONFINITE, FILTER_BAD_EXTENT = 1, 2
 GATHER_ID_BYTES = 128
 
 

@@ -1,0 +1,239 @@
+"""Point clouds on the device and their cleanup filters (``csrc/cloud_filter.hip``).
+
+``PointCloud`` is a packed float64 ``xyz`` + uint8 BGR ``bgr`` pair in HBM; :func:`radius_outlier`
+and :func:`statistical_outlier` are the two deterministic neighbour filters of the reference's
+cleanup tab (``ProcessingLogic.remove_radius_outlier``, ``server/processing.py:430-448``, and
+``ProcessingLogic.remove_outliers``, ``server/processing.py:367-388``), run on that cloud without
+the PLY round trip through the host.  Semantics: ``include/slgpu.h`` and DESIGN.md §9 (Open3D's
+published rules restated; parity with an installed Open3D is unpinned).
+
+The PLY reader takes exactly the file ``ProcessingLogic._save_ply`` writes (``ply.header``): ASCII,
+``x y z red green blue``.  Anything else raises ``ValueError`` saying what differs.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+
+import numpy as np
+import torch
+
+from . import _native as N
+from . import engine as E
+from . import ply as PLY
+
+MAX_NEIGHBORS = 64          # kMaxK of csrc/cloud_filter.hip
+
+_HEADER_TAIL = PLY.header(0).decode().split("\n")[3:-1]      # the property lines + end_header
+
+
+def read_ply(path):
+    """``(P float64 [n, 3], C uint8 [n, 3] BGR)`` of an ASCII PLY in ``_save_ply``'s layout."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply\n"):
+        raise ValueError(f"{path}: not a PLY file (no 'ply' magic line)")
+    if end < 0:
+        raise ValueError(f"{path}: PLY header has no end_header line")
+    lines = data[:end + len(b"end_header")].decode("ascii", errors="replace").split("\n")
+    if len(lines) < 3 or lines[1] != "format ascii 1.0":
+        raise ValueError(f"{path}: only 'format ascii 1.0' PLY files are read, this one says "
+                         f"{lines[1] if len(lines) > 1 else ''!r}")
+    parts = lines[2].split()
+    if len(parts) != 3 or parts[:2] != ["element", "vertex"] or not parts[2].isdigit():
+        raise ValueError(f"{path}: expected 'element vertex <n>' as the third header line, got {lines[2]!r}")
+    n = int(parts[2])
+    if lines[3:] != _HEADER_TAIL:
+        raise ValueError(f"{path}: the vertex layout must be exactly {_HEADER_TAIL[:-1]} "
+                         f"(what _save_ply writes), got {lines[3:-1]}")
+    body = data[end + len(b"end_header\n"):]
+    try:
+        vals = np.array(body.split(), dtype=np.float64)
+    except ValueError as e:
+        raise ValueError(f"{path}: a vertex line holds something that is not a number ({e})") from None
+    if vals.size != 6 * n:
+        raise ValueError(f"{path}: header promises {n} vertices of 6 values, body holds {vals.size} values")
+    vals = vals.reshape(n, 6)
+    rgb = vals[:, 3:]
+    if n and not (np.all(rgb == np.floor(rgb)) and rgb.min() >= 0 and rgb.max() <= 255):
+        raise ValueError(f"{path}: colours must be integers 0..255")
+    return np.ascontiguousarray(vals[:, :3]), np.ascontiguousarray(rgb[:, ::-1].astype(np.uint8))
+
+
+class PointCloud:
+    """A cloud in HBM: ``xyz`` float64 ``[n, 3]`` and ``bgr`` uint8 ``[n, 3]`` (an empty cloud
+    holds empty host tensors and needs no device).
+
+    Build it from ``(P, C)`` arrays or tensors, from an ``engine.Cloud`` (:meth:`from_cloud`, the
+    points stay on the device) or from a PLY written by ``_save_ply`` (:meth:`from_file`)."""
+
+    def __init__(self, points, colors=None, device=None):
+        def as_tensor(a, dt, np_dt):
+            if isinstance(a, torch.Tensor):
+                return a.reshape(-1, 3).to(dt)
+            a = np.ascontiguousarray(np.asarray(a, dtype=np_dt).reshape(-1, 3))
+            return torch.from_numpy(a if a.flags.writeable else a.copy())
+
+        xyz = as_tensor(points, torch.float64, np.float64)
+        if colors is None:
+            colors = np.zeros((len(xyz), 3), np.uint8)
+        bgr = as_tensor(colors, torch.uint8, np.uint8)
+        if len(xyz) != len(bgr):
+            raise ValueError("points and colors differ in length")
+        if len(xyz):
+            dev = device or (xyz.device if xyz.is_cuda else E.default_device())
+            xyz, bgr = xyz.to(dev).contiguous(), bgr.to(dev).contiguous()
+        self.xyz, self.bgr = xyz, bgr
+
+    @classmethod
+    def from_cloud(cls, cloud: "E.Cloud") -> "PointCloud":
+        """From a reconstructed view (``Reconstructor.reconstruct(..., xyz_f64=True)``): reads the
+        point count, copies no point."""
+        if not cloud.xyz_f64:
+            raise ValueError("PointCloud needs a float64 cloud (reconstruct with xyz_f64=True)")
+        P, C = cloud.result()
+        return cls(P, C)
+
+    @classmethod
+    def from_file(cls, path) -> "PointCloud":
+        return cls(*read_ply(path))
+
+    def has_points(self) -> bool:
+        return len(self) > 0
+
+    def __len__(self) -> int:
+        return int(self.xyz.shape[0])
+
+    def numpy(self):
+        """Host ``(P float64 [n, 3], C uint8 [n, 3] BGR)``."""
+        return self.xyz.cpu().numpy(), self.bgr.cpu().numpy()
+
+    def save(self, path) -> None:
+        """ASCII PLY as ``_save_ply`` writes it."""
+        PLY.write_ascii(path, *self.numpy())
+
+
+def as_point_cloud(obj) -> PointCloud:
+    if isinstance(obj, PointCloud):
+        return obj
+    if isinstance(obj, E.Cloud):
+        return PointCloud.from_cloud(obj)
+    if isinstance(obj, (str, os.PathLike)):
+        return PointCloud.from_file(obj)
+    if isinstance(obj, (tuple, list)) and len(obj) == 2:
+        return PointCloud(*obj)
+    raise TypeError(f"cannot make a PointCloud from {type(obj).__name__}")
+
+
+# ----------------------------------------------------------------------------- filters
+_WS: dict = {}
+
+
+def _workspace(n: int, k: int, device) -> torch.Tensor:
+    need = int(N.lib().slg_filter_ws_bytes(n, k))
+    if need < 0:
+        N.check(-need)
+    ws = _WS.get(device)
+    if ws is None or ws.numel() < need:
+        ws = _WS[device] = torch.empty(need, dtype=torch.uint8, device=device)
+    return ws
+
+
+def _check_xyz(xyz: torch.Tensor) -> torch.Tensor:
+    if not (isinstance(xyz, torch.Tensor) and xyz.is_cuda and xyz.dtype == torch.float64
+            and xyz.ndim == 2 and xyz.shape[1] == 3):
+        raise ValueError("the cloud filters take a device float64 [n, 3] tensor")
+    if xyz.shape[0] == 0:
+        raise ValueError("Point cloud is empty.")
+    return xyz.contiguous()
+
+
+def _check_status(ws: torch.Tensor, what: str) -> None:
+    """Reads the status word at the front of the workspace (synchronises the stream)."""
+    status = int(ws[:4].view(torch.int32).item())
+    if status & N.FILTER_BAD_NONFINITE:
+        raise ValueError(f"{what}: the cloud holds a NaN or infinite coordinate")
+    if status & N.FILTER_BAD_EXTENT:
+        raise ValueError(f"{what}: the cloud spans 2^21 or more cells of the radius on an axis")
+
+
+def far_count(device) -> int:
+    """Points the last :func:`statistical_mask` on ``device`` sent to the whole-cloud kernel (the
+    ring walk reached its cap): the int32 at byte 8 of the workspace.  A test hook."""
+    return int(_WS[device][8:12].view(torch.int32).item())
+
+
+def radius_mask(xyz: torch.Tensor, nb_points: int, radius: float, stream=None):
+    """``(keep uint8 [n], counts int32 [n])`` on the device: ``counts[i]`` = points with
+    ``d2 < radius**2`` (``i`` included), ``keep = counts > nb_points``."""
+    xyz = _check_xyz(xyz)
+    n = xyz.shape[0]
+    with torch.cuda.device(xyz.device):
+        ws = _workspace(n, 0, xyz.device)
+        keep = torch.empty(n, dtype=torch.uint8, device=xyz.device)
+        counts = torch.empty(n, dtype=torch.int32, device=xyz.device)
+        rc = N.lib().slg_radius_outlier(E._vp(xyz), n, float(radius), int(nb_points), E._vp(ws), ws.numel(),
+                                        E._vp(keep), E._vp(counts), E._stream(stream))
+        _raise(rc)
+        _check_status(ws, "radius_outlier")
+    return keep, counts
+
+
+def statistical_mask(xyz: torch.Tensor, nb_neighbors: int, std_ratio: float, stream=None):
+    """``(keep uint8 [n], avg float64 [n], stats float64 [3] = mean, std, thr)`` on the device."""
+    xyz = _check_xyz(xyz)
+    n = xyz.shape[0]
+    with torch.cuda.device(xyz.device):
+        ws = _workspace(n, min(int(nb_neighbors), MAX_NEIGHBORS), xyz.device)
+        keep = torch.empty(n, dtype=torch.uint8, device=xyz.device)
+        avg = torch.empty(n, dtype=torch.float64, device=xyz.device)
+        stats = torch.empty(3, dtype=torch.float64, device=xyz.device)
+        rc = N.lib().slg_statistical_outlier(E._vp(xyz), n, int(nb_neighbors), float(std_ratio), E._vp(ws),
+                                             ws.numel(), E._vp(keep), E._vp(avg), E._vp(stats), E._stream(stream))
+        _raise(rc)
+        _check_status(ws, "statistical_outlier")
+    return keep, avg, stats
+
+
+def _raise(rc: int) -> None:
+    if rc == N.SLG_ERR_INVALID:
+        raise ValueError(N.lib().slg_last_error().decode(errors="replace"))
+    N.check(rc)
+
+
+def select(pc: PointCloud, keep: torch.Tensor, stream=None):
+    """``(PointCloud of the points with keep != 0 in input order, their indices int64)``."""
+    n = len(pc)
+    dev = pc.xyz.device
+    with torch.cuda.device(dev):
+        ws = _workspace(n, 0, dev)
+        out = E.Cloud(n, 0, True, dev)
+        index = torch.empty(n, dtype=torch.int64, device=dev)
+        o = out.struct()
+        _raise(N.lib().slg_cloud_select(E._vp(pc.xyz), E._vp(pc.bgr), n, E._vp(keep.contiguous()), ctypes.byref(o),
+                                        E._vp(index), E._vp(ws), E._stream(stream)))
+        P, C = out._launched_on(stream).result()
+    return PointCloud(P, C), index[:len(P)]
+
+
+def radius_outlier(pc, nb_points: int, radius: float, return_index: bool = False):
+    """Open3D ``remove_radius_outlier`` + ``select_by_index`` on the device: a new ``PointCloud``
+    of the points with more than ``nb_points`` points (itself included) closer than ``radius``."""
+    pc = as_point_cloud(pc)
+    if not pc.has_points():
+        raise ValueError("Point cloud is empty.")
+    keep, _ = radius_mask(pc.xyz, nb_points, radius)
+    out, idx = select(pc, keep)
+    return (out, idx) if return_index else out
+
+
+def statistical_outlier(pc, nb_neighbors: int, std_ratio: float, return_index: bool = False):
+    """Open3D ``remove_statistical_outlier`` + ``select_by_index`` on the device
+    (``nb_neighbors`` <= 64)."""
+    pc = as_point_cloud(pc)
+    if not pc.has_points():
+        raise ValueError("Point cloud is empty.")
+    keep, _, _ = statistical_mask(pc.xyz, nb_neighbors, std_ratio)
+    out, idx = select(pc, keep)
+    return (out, idx) if return_index else out

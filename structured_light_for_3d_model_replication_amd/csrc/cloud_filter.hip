@@ -1,0 +1,733 @@
+// cloud_filter.hip — device point-cloud cleanup for gfx950: radius and statistical outlier
+// removal over a packed fp64 cloud, and the order-preserving select that follows them
+// (ProcessingLogic.remove_radius_outlier, server/processing.py:430-448, and
+// ProcessingLogic.remove_outliers, server/processing.py:367-388).
+//
+// The semantics are Open3D's PointCloud::RemoveRadiusOutliers / RemoveStatisticalOutliers as
+// published, restated (parity with an installed Open3D is unpinned).  Each rule
+// lives in exactly one __device__ function below (d2_rule, radius_keep_rule, avg_rule,
+// stat_threshold_rule, stat_keep_rule); tests/cloud_ref.py holds the same rules for NumPy.
+//
+// Both filters share one structure, a sparse uniform grid:
+//   bbox (fixed-order reduction) -> integer cell coordinates floor((p - min) / cell) packed into
+//   a 63-bit key (21 bits per axis, x lowest) -> stable radix sort of (key, index) -> points
+//   gathered in sorted order -> table of unique keys + start offsets (binary search).
+// x is the lowest key field, so the cells x0..x1 of one (y, z) row are one contiguous range of
+// the sorted cloud: a 3x3x3 neighbourhood is 9 ranges.  No dense cell array exists, so far
+// outliers (row_mode 2 clouds) cost nothing.
+//
+// Everything is separate launches on the caller's stream; no workgroup waits for another and
+// nothing synchronises with the host.  Conditions only the device can see (a non-finite
+// coordinate, an axis of 2^21 cells or more) set a status word at the front of the workspace;
+// every later kernel of the call reads it and returns, so a bad input ends in the flag.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <math.h>
+#include <string.h>
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/functional.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
+
+#include "../../include/slgpu.h"
+
+int slg_internal_fail(int code, const char* fmt, ...);
+
+namespace {
+
+constexpr int kCellBits = 21;
+constexpr int64_t kCellMax = (1ll << kCellBits) - 1;
+constexpr int kMaxK = 64;
+constexpr int kTile = 1024;        // candidate points staged in LDS per tile (24 KB)
+constexpr int kChunk = 2048;       // points per workgroup in the fixed-order reductions
+constexpr int kMaxRing = 6;        // Chebyshev rings the kNN walk takes before the whole-cloud kernel
+constexpr double kInf = __builtin_huge_val();
+
+// ---------------------------------------------------------------- the rules (one place each)
+// Squared distance: the same expression, in the same order, as tests/cloud_ref.py:d2.
+__device__ inline double d2_rule(double dx, double dy, double dz) { return (dx * dx + dy * dy) + dz * dz; }
+// A neighbour counts when d2 < radius^2 (strict); the point itself counts.
+__device__ inline bool radius_neighbour_rule(double d2, double r2) { return d2 < r2; }
+__device__ inline bool radius_keep_rule(int32_t count, int32_t nb_points) { return count > nb_points; }
+// Mean distance to the min(k, N) nearest (self included): sqrt of each d2, summed ascending, / kk.
+__device__ inline double avg_rule(double sum_sqrt, int kk) { return sum_sqrt / (double)kk; }
+__device__ inline bool stat_counts_rule(double avg) { return avg > 0.0; }
+__device__ inline bool stat_keep_rule(double avg, double thr) { return avg > 0.0 && avg < thr; }
+
+// ---------------------------------------------------------------- workspace
+struct Hdr {            // 256 bytes at the front of the workspace
+  int32_t status;       // SLG_FILTER_BAD_* bits
+  int32_t n_unique;
+  int32_t n_far;
+  int32_t pad;
+  double mn[3], mx[3];
+  double cell;
+  double slack;         // absolute rounding allowance on a face distance
+  int32_t cmax[3];
+  int32_t pad2;
+  double mean, std, thr;
+};
+static_assert(sizeof(Hdr) <= 256, "header");
+
+struct Layout {
+  size_t keys, keys_s, idx, idx_s, sxyz, pos, ukeys, ustart, part, avg, far, temp, temp_bytes, total;
+};
+
+size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct U8ToU32 {
+  __host__ __device__ uint32_t operator()(uint8_t v) const { return v ? 1u : 0u; }
+};
+
+hipError_t temp_bytes_for(int64_t n, size_t* out) {
+  size_t a = 0, b = 0, c = 0;
+  hipError_t e = rocprim::radix_sort_pairs(nullptr, a, (const uint64_t*)nullptr, (uint64_t*)nullptr,
+                                           (const uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n, 0u, 63u,
+                                           (hipStream_t)0);
+  if (e != hipSuccess) return e;
+  e = rocprim::exclusive_scan(nullptr, b, (const uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)n,
+                              rocprim::plus<uint32_t>(), (hipStream_t)0);
+  if (e != hipSuccess) return e;
+  auto it = rocprim::make_transform_iterator((const uint8_t*)nullptr, U8ToU32());
+  e = rocprim::exclusive_scan(nullptr, c, it, (uint32_t*)nullptr, 0u, (size_t)n, rocprim::plus<uint32_t>(),
+                              (hipStream_t)0);
+  if (e != hipSuccess) return e;
+  *out = a > b ? (a > c ? a : c) : (b > c ? b : c);
+  return hipSuccess;
+}
+
+Layout make_layout(int64_t n, size_t temp_bytes) {
+  Layout L;
+  size_t o = 256;
+  const size_t N = (size_t)n;
+  L.keys = o;   o = up256(o + N * 8);
+  L.keys_s = o; o = up256(o + N * 8);
+  L.idx = o;    o = up256(o + N * 4);
+  L.idx_s = o;  o = up256(o + N * 4);
+  L.sxyz = o;   o = up256(o + N * 24);
+  L.pos = o;    o = up256(o + N * 4);
+  L.ukeys = o;  o = up256(o + N * 8);
+  L.ustart = o; o = up256(o + (N + 1) * 4);
+  L.part = o;   o = up256(o + ((N + kChunk - 1) / kChunk) * 6 * 8);
+  L.avg = o;    o = up256(o + N * 8);
+  L.far = o;    o = up256(o + N * 4);
+  L.temp = o;   o = up256(o + temp_bytes);
+  L.temp_bytes = temp_bytes;
+  L.total = o;
+  return L;
+}
+
+// ---------------------------------------------------------------- grid helpers
+__device__ inline int64_t cell_coord(double p, double mn, double cell) {
+  const double c = floor((p - mn) / cell);
+  if (!(c > 0.0)) return 0;                 // also NaN
+  return c > (double)kCellMax ? kCellMax : (int64_t)c;
+}
+__device__ inline uint64_t pack_key(int64_t x, int64_t y, int64_t z) {
+  return ((uint64_t)z << (2 * kCellBits)) | ((uint64_t)y << kCellBits) | (uint64_t)x;
+}
+// First table entry with key >= k (nu when none).
+__device__ inline int lower_bound(const uint64_t* __restrict__ a, int nu, uint64_t k) {
+  int lo = 0, hi = nu;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (a[mid] < k) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+// Sorted-cloud range [s, e) of the cells x0..x1 of row (y, z).
+__device__ inline void row_range(const uint64_t* __restrict__ ukeys, const uint32_t* __restrict__ ustart, int nu,
+                                 int64_t x0, int64_t x1, int64_t y, int64_t z, uint32_t* s, uint32_t* e) {
+  const int u0 = lower_bound(ukeys, nu, pack_key(x0, y, z));
+  const int u1 = lower_bound(ukeys, nu, pack_key(x1, y, z) + 1);
+  *s = ustart[u0];                           // ustart[nu] = n
+  *e = ustart[u1];
+}
+
+// ---------------------------------------------------------------- bounding box (fixed order)
+__global__ __launch_bounds__(256) void bbox_partial_kernel(const double* __restrict__ xyz, int64_t n, Hdr* hdr,
+                                                           double* __restrict__ part) {
+  __shared__ double sm[6][256];
+  const int t = threadIdx.x;
+  double lo[3] = {kInf, kInf, kInf}, hi[3] = {-kInf, -kInf, -kInf};
+  bool bad = false;
+  const int64_t base = (int64_t)blockIdx.x * kChunk;
+  for (int j = 0; j < kChunk / 256; ++j) {
+    const int64_t i = base + j * 256 + t;
+    if (i < n) {
+      for (int a = 0; a < 3; ++a) {
+        const double v = xyz[3 * i + a];
+        if (!isfinite(v)) bad = true;
+        lo[a] = fmin(lo[a], v);
+        hi[a] = fmax(hi[a], v);
+      }
+    }
+  }
+  if (bad) atomicOr(&hdr->status, SLG_FILTER_BAD_NONFINITE);
+  for (int a = 0; a < 3; ++a) { sm[a][t] = lo[a]; sm[3 + a][t] = hi[a]; }
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s)
+      for (int a = 0; a < 3; ++a) {
+        sm[a][t] = fmin(sm[a][t], sm[a][t + s]);
+        sm[3 + a][t] = fmax(sm[3 + a][t], sm[3 + a][t + s]);
+      }
+    __syncthreads();
+  }
+  if (t < 6) part[(int64_t)blockIdx.x * 6 + t] = sm[t][0];
+}
+
+__device__ inline void set_cell(Hdr* hdr, double cell) {
+  hdr->cell = cell;
+  for (int a = 0; a < 3; ++a) hdr->cmax[a] = (int32_t)cell_coord(hdr->mx[a], hdr->mn[a], cell);
+}
+
+// Points per occupied cell the kNN grid aims for: the k nearest then lie within about one cell
+// size, so the walk usually ends after ring 1.
+__device__ inline double knn_target(int k) { return fmax(2.0, (double)k / 4.0); }
+
+// One workgroup: folds the partial boxes, then fixes the cell size.  cell_in > 0: the radius
+// filter's cell (= radius), and an axis of 2^21 cells or more is flagged.  cell_in <= 0: the kNN
+// grid's first guess from the box alone; knn_refine_kernel corrects it from the occupancy.
+__global__ __launch_bounds__(256) void bbox_final_kernel(const double* __restrict__ part, int nb, Hdr* hdr,
+                                                         double cell_in, int64_t n, int k) {
+  __shared__ double sm[6][256];
+  const int t = threadIdx.x;
+  double lo[3] = {kInf, kInf, kInf}, hi[3] = {-kInf, -kInf, -kInf};
+  for (int b = t; b < nb; b += 256)
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = fmin(lo[a], part[(int64_t)b * 6 + a]);
+      hi[a] = fmax(hi[a], part[(int64_t)b * 6 + 3 + a]);
+    }
+  for (int a = 0; a < 3; ++a) { sm[a][t] = lo[a]; sm[3 + a][t] = hi[a]; }
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s)
+      for (int a = 0; a < 3; ++a) {
+        sm[a][t] = fmin(sm[a][t], sm[a][t + s]);
+        sm[3 + a][t] = fmax(sm[3 + a][t], sm[3 + a][t + s]);
+      }
+    __syncthreads();
+  }
+  if (t != 0 || hdr->status) return;
+  double ext = 0.0, mag = 0.0;
+  for (int a = 0; a < 3; ++a) {
+    hdr->mn[a] = sm[a][0];
+    hdr->mx[a] = sm[3 + a][0];
+    ext = fmax(ext, sm[3 + a][0] - sm[a][0]);
+    mag = fmax(mag, fmax(fabs(sm[a][0]), fabs(sm[3 + a][0])));
+  }
+  if (!isfinite(ext)) { atomicOr(&hdr->status, SLG_FILTER_BAD_EXTENT); return; }   // max - min overflowed
+  hdr->slack = 0x1p-49 * fmax(mag, ext);
+  if (cell_in > 0.0) {
+    if (ext / cell_in >= (double)(kCellMax + 1)) { atomicOr(&hdr->status, SLG_FILTER_BAD_EXTENT); return; }
+    set_cell(hdr, cell_in);
+  } else {
+    // a surface filling the box's largest face would put knn_target(k) points in a cell of this size
+    double e[3] = {sm[3][0] - sm[0][0], sm[4][0] - sm[1][0], sm[5][0] - sm[2][0]};
+    const double smallest = fmin(e[0], fmin(e[1], e[2]));
+    const double area = smallest > 0.0 ? e[0] * e[1] * e[2] / smallest : fmax(e[0] * e[1], fmax(e[0] * e[2], e[1] * e[2]));
+    double cell = sqrt(area * knn_target(k) / (double)n);
+    if (!(cell > 0.0) || !isfinite(cell)) cell = ext > 0.0 ? ext / 1024.0 : 1.0;
+    set_cell(hdr, fmax(cell, ext / (double)(1 << 20)));
+  }
+}
+
+// kNN cell from occupancy: with o = N / (occupied cells) points per occupied cell and a cloud that
+// is a surface (o ~ cell^2), rescale the cell so that an occupied cell holds about knn_target(k)
+// points (far outliers inflate the box, so the first guess can be far too large); a factor of two
+// either way is left alone; never below extent / 2^20 cells per axis.  Run between grid builds.
+__global__ void knn_refine_kernel(Hdr* hdr, int64_t n, int k) {
+  if (hdr->status || hdr->n_unique <= 0) return;
+  const double target = knn_target(k);
+  const double occ = (double)n / (double)hdr->n_unique;
+  if (occ <= 2.0 * target && occ >= 0.5 * target) return;
+  double ext = 0.0;
+  for (int a = 0; a < 3; ++a) ext = fmax(ext, hdr->mx[a] - hdr->mn[a]);
+  if (!(ext > 0.0)) return;
+  double cell = hdr->cell * fmin(fmax(sqrt(target / occ), 1.0 / 64.0), 4.0);
+  set_cell(hdr, fmax(cell, ext / (double)(1 << 20)));
+}
+
+// ---------------------------------------------------------------- grid build
+__global__ __launch_bounds__(256) void keys_kernel(const double* __restrict__ xyz, int64_t n, const Hdr* hdr,
+                                                   uint64_t* __restrict__ keys, uint32_t* __restrict__ idx) {
+  if (hdr->status) return;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double cell = hdr->cell;
+  keys[i] = pack_key(cell_coord(xyz[3 * i], hdr->mn[0], cell), cell_coord(xyz[3 * i + 1], hdr->mn[1], cell),
+                     cell_coord(xyz[3 * i + 2], hdr->mn[2], cell));
+  idx[i] = (uint32_t)i;
+}
+
+// Sorted copy of the points, and the run-start flags of the sorted keys.
+__global__ __launch_bounds__(256) void gather_flags_kernel(const double* __restrict__ xyz, int64_t n, const Hdr* hdr,
+                                                           const uint64_t* __restrict__ keys_s,
+                                                           const uint32_t* __restrict__ idx_s,
+                                                           double* __restrict__ sxyz, uint32_t* __restrict__ flags) {
+  if (hdr->status) return;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t src = idx_s[i];
+  sxyz[3 * i] = xyz[3 * src];
+  sxyz[3 * i + 1] = xyz[3 * src + 1];
+  sxyz[3 * i + 2] = xyz[3 * src + 2];
+  flags[i] = (i == 0 || keys_s[i] != keys_s[i - 1]) ? 1u : 0u;
+}
+
+// pos = exclusive scan of the run-start flags: run start i is table entry pos[i].
+__global__ __launch_bounds__(256) void table_kernel(int64_t n, Hdr* hdr, const uint64_t* __restrict__ keys_s,
+                                                    const uint32_t* __restrict__ pos, uint64_t* __restrict__ ukeys,
+                                                    uint32_t* __restrict__ ustart) {
+  if (hdr->status) return;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const bool start = i == 0 || keys_s[i] != keys_s[i - 1];
+  if (start) {
+    ukeys[pos[i]] = keys_s[i];
+    ustart[pos[i]] = (uint32_t)i;
+  }
+  if (i == n - 1) {
+    const uint32_t nu = pos[i] + (start ? 1u : 0u);
+    ustart[nu] = (uint32_t)n;
+    hdr->n_unique = (int32_t)nu;
+  }
+}
+
+// ---------------------------------------------------------------- radius count
+// One workgroup per occupied cell (grid-stride).  The cell's points are the queries, one per
+// thread, 256 at a time; the candidates are the 9 row ranges of the 3x3x3 block, staged through
+// LDS in tiles of kTile points and read back as broadcasts (every lane the same address), so the
+// inner loop is fp64 VALU fed from LDS.  A wave none of whose lanes holds a query skips the loop.
+__global__ __launch_bounds__(256) void radius_count_kernel(const Hdr* hdr, const double* __restrict__ sxyz,
+                                                           const uint32_t* __restrict__ sidx,
+                                                           const uint64_t* __restrict__ ukeys,
+                                                           const uint32_t* __restrict__ ustart, double r2,
+                                                           int32_t nb_points, uint8_t* __restrict__ keep,
+                                                           int32_t* __restrict__ counts) {
+  __shared__ double tile[3 * kTile];
+  __shared__ uint32_t rng[9][2];
+  if (hdr->status) return;
+  const int nu = hdr->n_unique;
+  const int t = threadIdx.x;
+  for (int u = blockIdx.x; u < nu; u += gridDim.x) {
+    const uint64_t key = ukeys[u];
+    const int64_t cx = key & kCellMax, cy = (key >> kCellBits) & kCellMax, cz = (key >> (2 * kCellBits)) & kCellMax;
+    const uint32_t qs = ustart[u], qe = ustart[u + 1];
+    __syncthreads();                         // the previous cell's ranges are no longer read
+    if (t < 9) {
+      const int64_t y = cy + (t % 3) - 1, z = cz + (t / 3) - 1;
+      uint32_t s = 0, e = 0;
+      if (y >= 0 && y <= hdr->cmax[1] && z >= 0 && z <= hdr->cmax[2])
+        row_range(ukeys, ustart, nu, cx > 0 ? cx - 1 : 0, cx < hdr->cmax[0] ? cx + 1 : cx, y, z, &s, &e);
+      rng[t][0] = s;
+      rng[t][1] = e;
+    }
+    __syncthreads();
+    for (uint32_t qb = qs; qb < qe; qb += 256) {
+      const uint32_t q = qb + t;
+      const bool active = q < qe;
+      const bool wave_active = qb + (uint32_t)(t & ~63) < qe;
+      double px = 0.0, py = 0.0, pz = 0.0;
+      if (active) { px = sxyz[3 * (size_t)q]; py = sxyz[3 * (size_t)q + 1]; pz = sxyz[3 * (size_t)q + 2]; }
+      int32_t cnt = 0;
+      for (int r = 0; r < 9; ++r) {
+        const uint32_t s = rng[r][0], e = rng[r][1];
+        for (uint32_t tb = s; tb < e; tb += kTile) {
+          const int m = (int)(e - tb < (uint32_t)kTile ? e - tb : (uint32_t)kTile);
+          __syncthreads();                   // the previous tile has been consumed
+          for (int w = t; w < 3 * m; w += 256) tile[w] = sxyz[3 * (size_t)tb + w];
+          __syncthreads();
+          if (wave_active) {
+#pragma unroll 4
+            for (int j = 0; j < m; ++j) {
+              const double d2 = d2_rule(tile[3 * j] - px, tile[3 * j + 1] - py, tile[3 * j + 2] - pz);
+              cnt += radius_neighbour_rule(d2, r2) ? 1 : 0;
+            }
+          }
+        }
+      }
+      if (active) {
+        const uint32_t o = sidx[q];
+        keep[o] = radius_keep_rule(cnt, nb_points) ? 1 : 0;
+        if (counts) counts[o] = cnt;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------- kNN
+// Per-lane top-kk list of d2 in LDS, lst[j * 64 + lane] (lanes on consecutive addresses):
+// unsorted while filling, with the largest entry tracked; once full, a smaller d2 replaces the
+// largest and the list is rescanned for the new one.
+struct TopK {
+  double* lst;      // this lane's column
+  int kk, cnt, maxpos;
+  double curmax;
+  __device__ inline void insert(double d) {
+    if (cnt < kk) {
+      lst[cnt * 64] = d;
+      if (d > curmax) { curmax = d; maxpos = cnt; }
+      ++cnt;
+    } else if (d < curmax) {
+      lst[maxpos * 64] = d;
+      double m = -1.0;
+      int mp = 0;
+      for (int j = 0; j < kk; ++j) {
+        const double v = lst[j * 64];
+        if (v > m) { m = v; mp = j; }
+      }
+      curmax = m;
+      maxpos = mp;
+    }
+  }
+  __device__ inline void sort() {            // ascending insertion sort of the cnt entries
+    for (int a = 1; a < cnt; ++a) {
+      const double v = lst[a * 64];
+      int b = a - 1;
+      while (b >= 0 && lst[b * 64] > v) { lst[(b + 1) * 64] = lst[b * 64]; --b; }
+      lst[(b + 1) * 64] = v;
+    }
+  }
+};
+
+__device__ inline void scan_range(TopK& tk, const double* __restrict__ sxyz, uint32_t s, uint32_t e, double px,
+                                  double py, double pz) {
+  for (uint32_t j = s; j < e; ++j)
+    tk.insert(d2_rule(sxyz[3 * (size_t)j] - px, sxyz[3 * (size_t)j + 1] - py, sxyz[3 * (size_t)j + 2] - pz));
+}
+
+// One point per thread: cells in Chebyshev rings around the point's cell until the list is full
+// and its largest d2 is no larger than the squared distance to the nearest face of the block
+// searched (faces at or past the cloud's box do not count: nothing lies beyond them).  The face
+// distance gives up the header's absolute slack and a relative 1e-12, so rounding in the cell
+// coordinates cannot end the walk early.  Points still open after kMaxRing rings go to the list
+// of knn_far_kernel.
+__global__ __launch_bounds__(64) void knn_kernel(Hdr* hdr, const double* __restrict__ sxyz,
+                                                 const uint32_t* __restrict__ sidx,
+                                                 const uint64_t* __restrict__ ukeys,
+                                                 const uint32_t* __restrict__ ustart, int64_t n, int k,
+                                                 double* __restrict__ avg, uint32_t* __restrict__ far) {
+  extern __shared__ double lds[];
+  if (hdr->status) return;
+  const int64_t q = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (q >= n) return;
+  const int nu = hdr->n_unique;
+  const double h = hdr->cell;
+  const double p[3] = {sxyz[3 * q], sxyz[3 * q + 1], sxyz[3 * q + 2]};
+  int64_t c[3], cm[3];
+  for (int a = 0; a < 3; ++a) { c[a] = cell_coord(p[a], hdr->mn[a], h); cm[a] = hdr->cmax[a]; }
+  TopK tk{lds + threadIdx.x, (int)(n < k ? n : k), 0, 0, -1.0};
+  bool done = false;
+  for (int R = 0; R <= kMaxRing && !done; ++R) {
+    for (int dz = -R; dz <= R; ++dz) {
+      const int64_t z = c[2] + dz;
+      if (z < 0 || z > cm[2]) continue;
+      for (int dy = -R; dy <= R; ++dy) {
+        const int64_t y = c[1] + dy;
+        if (y < 0 || y > cm[1]) continue;
+        uint32_t s, e;
+        if (abs(dy) == R || abs(dz) == R) {  // a whole row of the shell
+          row_range(ukeys, ustart, nu, c[0] - R < 0 ? 0 : c[0] - R, c[0] + R > cm[0] ? cm[0] : c[0] + R, y, z, &s, &e);
+          scan_range(tk, sxyz, s, e, p[0], p[1], p[2]);
+        } else {                             // the row's two end cells
+          if (c[0] - R >= 0) {
+            row_range(ukeys, ustart, nu, c[0] - R, c[0] - R, y, z, &s, &e);
+            scan_range(tk, sxyz, s, e, p[0], p[1], p[2]);
+          }
+          if (c[0] + R <= cm[0]) {
+            row_range(ukeys, ustart, nu, c[0] + R, c[0] + R, y, z, &s, &e);
+            scan_range(tk, sxyz, s, e, p[0], p[1], p[2]);
+          }
+        }
+      }
+    }
+    double bound = kInf;
+    for (int a = 0; a < 3; ++a) {
+      if (c[a] - R > 0) bound = fmin(bound, p[a] - (hdr->mn[a] + (double)(c[a] - R) * h));
+      if (c[a] + R < cm[a]) bound = fmin(bound, (hdr->mn[a] + (double)(c[a] + R + 1) * h) - p[a]);
+    }
+    if (bound == kInf) {
+      done = true;                           // the whole cloud has been searched
+    } else if (tk.cnt == tk.kk) {
+      const double b = fmax(bound - hdr->slack, 0.0);
+      done = tk.curmax <= (b * b) * (1.0 - 1e-12);
+    }
+  }
+  if (!done) {
+    far[atomicAdd(&hdr->n_far, 1)] = (uint32_t)q;      // list order is free: each entry is independent
+    return;
+  }
+  tk.sort();
+  double sum = 0.0;
+  for (int j = 0; j < tk.cnt; ++j) sum += sqrt(tk.lst[j * 64]);
+  avg[sidx[q]] = avg_rule(sum, tk.kk);
+}
+
+// One wave per listed point scans the whole cloud: each lane keeps the top-kk of its stride,
+// sorts it, and the wave merges the 64 sorted lists by taking the smallest head kk times, which
+// yields the distances in ascending order for the left-to-right sum.
+__global__ __launch_bounds__(64) void knn_far_kernel(const Hdr* hdr, const double* __restrict__ sxyz,
+                                                     const uint32_t* __restrict__ sidx, int64_t n, int k,
+                                                     double* __restrict__ avg, const uint32_t* __restrict__ far) {
+  extern __shared__ double lds[];
+  if (hdr->status) return;
+  const int lane = threadIdx.x;
+  const int nf = hdr->n_far;
+  const int kk = (int)(n < k ? n : k);
+  for (int f = blockIdx.x; f < nf; f += gridDim.x) {
+    const int64_t q = far[f];
+    const double px = sxyz[3 * q], py = sxyz[3 * q + 1], pz = sxyz[3 * q + 2];
+    TopK tk{lds + lane, kk, 0, 0, -1.0};
+    for (int64_t j = lane; j < n; j += 64)
+      tk.insert(d2_rule(sxyz[3 * j] - px, sxyz[3 * j + 1] - py, sxyz[3 * j + 2] - pz));
+    tk.sort();
+    int head = 0;
+    double sum = 0.0;
+    for (int r = 0; r < kk; ++r) {
+      const double v = head < tk.cnt ? tk.lst[head * 64] : kInf;
+      double m = v;
+      for (int s = 32; s > 0; s >>= 1) m = fmin(m, __shfl_xor(m, s, 64));
+      const unsigned long long who = __ballot(v == m);
+      if (lane == __ffsll((long long)who) - 1) ++head;
+      sum += sqrt(m);
+    }
+    if (lane == 0) avg[sidx[q]] = avg_rule(sum, kk);
+  }
+}
+
+// ---------------------------------------------------------------- statistics (fixed order)
+// Σ term(avg[i]) over the input order as a fixed tree: 8 consecutive elements per thread, a
+// binary tree over the workgroup's 256 threads, then (sum_final_kernel) thread t over partials
+// t, t + 256, ... and the same tree.  No atomics: two runs give the same bits.
+// MODE 0: term = avg (avg > 0).  MODE 1: term = (avg - mean)^2 (avg > 0).
+template <int MODE>
+__device__ inline double stat_term(double a, double mean) {
+  if (!stat_counts_rule(a)) return 0.0;
+  return MODE == 0 ? a : (a - mean) * (a - mean);
+}
+
+__device__ inline double block_tree_sum(double v, double* sm) {
+  const int t = threadIdx.x;
+  sm[t] = v;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) sm[t] = sm[t] + sm[t + s];
+    __syncthreads();
+  }
+  return sm[0];
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void sum_partial_kernel(const Hdr* hdr, const double* __restrict__ avg, int64_t n,
+                                                          double* __restrict__ part) {
+  __shared__ double sm[256];
+  if (hdr->status) return;
+  const double mean = hdr->mean;
+  const int64_t base = (int64_t)blockIdx.x * kChunk + threadIdx.x * (kChunk / 256);
+  double s = 0.0;
+  for (int j = 0; j < kChunk / 256; ++j)
+    if (base + j < n) s += stat_term<MODE>(avg[base + j], mean);
+  s = block_tree_sum(s, sm);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// mean = Σ / N; std = sqrt(Σ (avg - mean)^2 / (N - 1)); thr = mean + std_ratio * std.
+template <int MODE>
+__global__ __launch_bounds__(256) void sum_final_kernel(Hdr* hdr, const double* __restrict__ part, int nb, int64_t n,
+                                                        double std_ratio, double* __restrict__ stats_out) {
+  __shared__ double sm[256];
+  if (hdr->status) return;
+  double s = 0.0;
+  for (int b = threadIdx.x; b < nb; b += 256) s += part[b];
+  s = block_tree_sum(s, sm);
+  if (threadIdx.x != 0) return;
+  if (MODE == 0) {
+    hdr->mean = s / (double)n;
+  } else {
+    hdr->std = sqrt(s / (double)(n - 1));
+    hdr->thr = hdr->mean + std_ratio * hdr->std;
+    if (stats_out) { stats_out[0] = hdr->mean; stats_out[1] = hdr->std; stats_out[2] = hdr->thr; }
+  }
+}
+
+__global__ __launch_bounds__(256) void stat_keep_kernel(const Hdr* hdr, const double* __restrict__ avg, int64_t n,
+                                                        uint8_t* __restrict__ keep) {
+  if (hdr->status) return;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) keep[i] = stat_keep_rule(avg[i], hdr->thr) ? 1 : 0;
+}
+
+// ---------------------------------------------------------------- select
+__global__ __launch_bounds__(256) void select_kernel(const double* __restrict__ xyz, const uint8_t* __restrict__ bgr,
+                                                     int64_t n, const uint8_t* __restrict__ keep,
+                                                     const uint32_t* __restrict__ pos, double* __restrict__ oxyz,
+                                                     uint8_t* __restrict__ obgr, int64_t* __restrict__ count,
+                                                     int64_t capacity, int64_t* __restrict__ index_out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t j = pos[i];
+  if (keep[i] && j < capacity) {
+    for (int a = 0; a < 3; ++a) oxyz[3 * j + a] = xyz[3 * i + a];
+    if (bgr && obgr)
+      for (int a = 0; a < 3; ++a) obgr[3 * j + a] = bgr[3 * i + a];
+    if (index_out) index_out[j] = i;
+  }
+  if (i == n - 1) {
+    const int64_t total = j + (keep[i] ? 1 : 0);
+    *count = total < capacity ? total : capacity;
+  }
+}
+
+// ---------------------------------------------------------------- host side
+int launch_ok(const char* what) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return slg_internal_fail(SLG_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+  return SLG_OK;
+}
+
+int grid_of(int64_t n, int per) { return (int)((n + per - 1) / per); }
+
+struct Ws {
+  Hdr* hdr;
+  uint64_t *keys, *keys_s, *ukeys;
+  uint32_t *idx, *idx_s, *pos, *ustart, *far;
+  double *sxyz, *part, *avg;
+  void* temp;
+  size_t temp_bytes;
+};
+
+int bind_ws(const char* who, int64_t n, void* ws, int64_t ws_bytes, Ws* w) {
+  if (!ws || ((uintptr_t)ws & 7)) return slg_internal_fail(SLG_ERR_INVALID, "%s: workspace NULL or not 8-byte aligned", who);
+  size_t tb = 0;
+  if (temp_bytes_for(n, &tb) != hipSuccess) return slg_internal_fail(SLG_ERR_HIP, "%s: rocPRIM size query failed", who);
+  const Layout L = make_layout(n, tb);
+  if (ws_bytes >= 0 && (size_t)ws_bytes < L.total)
+    return slg_internal_fail(SLG_ERR_INVALID, "%s: workspace of %lld bytes, slg_filter_ws_bytes gives %lld", who,
+                             (long long)ws_bytes, (long long)L.total);
+  char* b = (char*)ws;
+  w->hdr = (Hdr*)b;
+  w->keys = (uint64_t*)(b + L.keys);     w->keys_s = (uint64_t*)(b + L.keys_s);
+  w->idx = (uint32_t*)(b + L.idx);       w->idx_s = (uint32_t*)(b + L.idx_s);
+  w->sxyz = (double*)(b + L.sxyz);       w->pos = (uint32_t*)(b + L.pos);
+  w->ukeys = (uint64_t*)(b + L.ukeys);   w->ustart = (uint32_t*)(b + L.ustart);
+  w->part = (double*)(b + L.part);       w->avg = (double*)(b + L.avg);
+  w->far = (uint32_t*)(b + L.far);       w->temp = b + L.temp;
+  w->temp_bytes = L.temp_bytes;
+  return SLG_OK;
+}
+
+// keys -> stable sort by key (so by original index within a key) -> sorted points -> cell table,
+// with the cell size the header holds.
+int build_grid(const double* xyz, int64_t n, const Ws& w, hipStream_t st) {
+  const int g = grid_of(n, 256);
+  keys_kernel<<<g, 256, 0, st>>>(xyz, n, w.hdr, w.keys, w.idx);
+  size_t tb = w.temp_bytes;
+  if (rocprim::radix_sort_pairs(w.temp, tb, (const uint64_t*)w.keys, w.keys_s, (const uint32_t*)w.idx, w.idx_s,
+                                (size_t)n, 0u, 63u, st) != hipSuccess)
+    return slg_internal_fail(SLG_ERR_HIP, "cloud filter: radix sort failed");
+  gather_flags_kernel<<<g, 256, 0, st>>>(xyz, n, w.hdr, w.keys_s, w.idx_s, w.sxyz, w.idx);   // idx: the flags
+  tb = w.temp_bytes;
+  if (rocprim::exclusive_scan(w.temp, tb, (const uint32_t*)w.idx, w.pos, 0u, (size_t)n, rocprim::plus<uint32_t>(),
+                              st) != hipSuccess)
+    return slg_internal_fail(SLG_ERR_HIP, "cloud filter: scan failed");
+  table_kernel<<<g, 256, 0, st>>>(n, w.hdr, w.keys_s, w.pos, w.ukeys, w.ustart);
+  return launch_ok("cloud filter grid build");
+}
+
+int bbox(const double* xyz, int64_t n, const Ws& w, double cell, int k, hipStream_t st) {
+  if (hipMemsetAsync(w.hdr, 0, 256, st) != hipSuccess) return slg_internal_fail(SLG_ERR_HIP, "cloud filter: memset failed");
+  const int nb = grid_of(n, kChunk);
+  bbox_partial_kernel<<<nb, 256, 0, st>>>(xyz, n, w.hdr, w.part);
+  bbox_final_kernel<<<1, 256, 0, st>>>(w.part, nb, w.hdr, cell, n, k);
+  return launch_ok("cloud filter bounding box");
+}
+
+constexpr int64_t kMaxPoints = 1ll << 30;    // 32-bit sorted indices and offsets
+
+}  // namespace
+
+extern "C" {
+
+int64_t slg_filter_ws_bytes(int64_t n, int32_t k) {
+  if (n <= 0 || k < 0) return -(int64_t)slg_internal_fail(SLG_ERR_INVALID, "slg_filter_ws_bytes: n <= 0 or k < 0");
+  if (n > kMaxPoints || k > kMaxK)
+    return -(int64_t)slg_internal_fail(SLG_ERR_UNSUPPORTED, "slg_filter_ws_bytes: more than 2^30 points or k > %d", kMaxK);
+  size_t tb = 0;
+  if (temp_bytes_for(n, &tb) != hipSuccess)
+    return -(int64_t)slg_internal_fail(SLG_ERR_HIP, "slg_filter_ws_bytes: rocPRIM size query failed");
+  return (int64_t)make_layout(n, tb).total;
+}
+
+int32_t slg_radius_outlier(const double* xyz, int64_t n, double radius, int32_t nb_points, void* ws, int64_t ws_bytes,
+                           uint8_t* keep_out, int32_t* counts_out, void* stream) {
+  if (n <= 0 || !(radius > 0.0) || !xyz || !keep_out)
+    return slg_internal_fail(SLG_ERR_INVALID, "slg_radius_outlier: n <= 0, radius <= 0 or a NULL buffer");
+  if (n > kMaxPoints) return slg_internal_fail(SLG_ERR_UNSUPPORTED, "slg_radius_outlier: more than 2^30 points");
+  Ws w;
+  int rc = bind_ws("slg_radius_outlier", n, ws, ws_bytes, &w);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  // cell = radius, widened by 2^-20: a pair the rule counts has |dx| < radius (1 + 2^-50), so its
+  // cell coordinates differ by less than 1 - 2^-20 + 2^-28 (the rounding of two coordinates below
+  // 2^21) and the pair always shares a 3x3x3 block, also when points sit exactly on cell faces
+  if ((rc = bbox(xyz, n, w, radius * (1.0 + 0x1p-20), 0, st))) return rc;
+  if ((rc = build_grid(xyz, n, w, st))) return rc;
+  const int64_t g = n < 8192 ? n : 8192;
+  radius_count_kernel<<<(int)g, 256, 0, st>>>(w.hdr, w.sxyz, w.idx_s, w.ukeys, w.ustart, radius * radius, nb_points,
+                                              keep_out, counts_out);
+  return launch_ok("radius_count_kernel");
+}
+
+int32_t slg_statistical_outlier(const double* xyz, int64_t n, int32_t nb_neighbors, double std_ratio, void* ws,
+                                int64_t ws_bytes, uint8_t* keep_out, double* avg_out, double* stats_out,
+                                void* stream) {
+  if (n <= 0 || nb_neighbors < 1 || !xyz || !keep_out)
+    return slg_internal_fail(SLG_ERR_INVALID, "slg_statistical_outlier: n <= 0, nb_neighbors < 1 or a NULL buffer");
+  if (nb_neighbors > kMaxK)
+    return slg_internal_fail(SLG_ERR_UNSUPPORTED, "slg_statistical_outlier: nb_neighbors > %d", kMaxK);
+  if (n > kMaxPoints) return slg_internal_fail(SLG_ERR_UNSUPPORTED, "slg_statistical_outlier: more than 2^30 points");
+  Ws w;
+  int rc = bind_ws("slg_statistical_outlier", n, ws, ws_bytes, &w);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int k = nb_neighbors;
+  if ((rc = bbox(xyz, n, w, 0.0, k, st))) return rc;
+  for (int pass = 0; pass < 3; ++pass) {       // first guess, then two occupancy refinements
+    if (pass) knn_refine_kernel<<<1, 1, 0, st>>>(w.hdr, n, k);
+    if ((rc = build_grid(xyz, n, w, st))) return rc;
+  }
+  double* avg = avg_out ? avg_out : w.avg;
+  const size_t lds = (size_t)(n < k ? n : k) * 64 * sizeof(double);
+  knn_kernel<<<grid_of(n, 64), 64, lds, st>>>(w.hdr, w.sxyz, w.idx_s, w.ukeys, w.ustart, n, k, avg, w.far);
+  knn_far_kernel<<<(int)(n < 1024 ? n : 1024), 64, lds, st>>>(w.hdr, w.sxyz, w.idx_s, n, k, avg, w.far);
+  const int nb = grid_of(n, kChunk);
+  sum_partial_kernel<0><<<nb, 256, 0, st>>>(w.hdr, avg, n, w.part);
+  sum_final_kernel<0><<<1, 256, 0, st>>>(w.hdr, w.part, nb, n, std_ratio, stats_out);
+  sum_partial_kernel<1><<<nb, 256, 0, st>>>(w.hdr, avg, n, w.part);
+  sum_final_kernel<1><<<1, 256, 0, st>>>(w.hdr, w.part, nb, n, std_ratio, stats_out);
+  stat_keep_kernel<<<grid_of(n, 256), 256, 0, st>>>(w.hdr, avg, n, keep_out);
+  return launch_ok("slg_statistical_outlier");
+}
+
+int32_t slg_cloud_select(const double* xyz, const uint8_t* bgr, int64_t n, const uint8_t* keep, const slg_cloud* out,
+                         int64_t* index_out, void* ws, void* stream) {
+  if (n <= 0 || !xyz || !keep || !out || !out->xyz || !out->count)
+    return slg_internal_fail(SLG_ERR_INVALID, "slg_cloud_select: n <= 0 or a NULL buffer");
+  if (n > kMaxPoints) return slg_internal_fail(SLG_ERR_UNSUPPORTED, "slg_cloud_select: more than 2^30 points");
+  Ws w;
+  int rc = bind_ws("slg_cloud_select", n, ws, -1, &w);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  size_t tb = w.temp_bytes;
+  auto it = rocprim::make_transform_iterator(keep, U8ToU32());
+  if (rocprim::exclusive_scan(w.temp, tb, it, w.pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), st) != hipSuccess)
+    return slg_internal_fail(SLG_ERR_HIP, "slg_cloud_select: scan failed");
+  select_kernel<<<grid_of(n, 256), 256, 0, st>>>(xyz, bgr, n, keep, w.pos, (double*)out->xyz, out->bgr, out->count,
+                                                out->capacity, index_out);
+  return launch_ok("select_kernel");
+}
+
+}  // extern "C"

@@ -2,9 +2,10 @@
 
 Same names, signatures, return types and error behaviour as the reference
 (``server/processing.py:27-334``); the arithmetic runs in the HIP kernels of ``libslgpu.so``.
-Only the reconstruction path is provided — the Open3D post-processing methods of the
-reference class (``remove_background`` ... ``mesh_360``, processing.py:336-860) are out of
-scope.
+The reconstruction path is provided, and of the Open3D post-processing methods of the
+reference class (``remove_background`` ... ``mesh_360``, processing.py:336-860) the two
+deterministic neighbour filters, ``remove_outliers`` and ``remove_radius_outlier``, which run
+on the device (``cloud.py``); the rest are out of scope.
 """
 from __future__ import annotations
 
@@ -353,6 +354,54 @@ class ProcessingLogic:
             success_count = BatchPipeline(cfg, calib_data, row_mode, epipolar_tol, group=batch_views(),
                                           log=log).run(subfolders, batch_write_stage())
             log(f"=== Batch Complete: {success_count}/{len(subfolders)} succeeded ===")
+
+    # --- Cleanup filters (device; cloud.py) ---
+    @staticmethod
+    def _load_pcd(input_data):
+        """``server/processing.py:15-24``: a path is read (``FileNotFoundError`` when missing),
+        anything else is taken as a cloud already in memory."""
+        from . import cloud as CL
+        if isinstance(input_data, str):
+            if not os.path.exists(input_data):
+                raise FileNotFoundError(f"Input file not found: {input_data}")
+            return CL.PointCloud.from_file(input_data)
+        return CL.as_point_cloud(input_data)
+
+    @staticmethod
+    def remove_outliers(input_data, output_path=None, nb_neighbors=20, std_ratio=2.0, return_obj=False):
+        """Statistical outlier removal on the device (``server/processing.py:367-388``).
+
+        Same signature, print lines and exceptions as the reference.  Two differences: the object
+        taken and returned is a ``cloud.PointCloud`` (not an Open3D one), and ``output_path`` is
+        written by ``_save_ply`` (ASCII PLY, which Open3D reads) instead of Open3D's binary PLY.
+        ``input_data``: a path to a PLY that ``_save_ply`` wrote, or a ``PointCloud``."""
+        from . import cloud as CL
+        print(f"[Outlier] Processing...")
+        pcd = ProcessingLogic._load_pcd(input_data)
+        if not pcd.has_points():
+            raise ValueError("Point cloud is empty.")
+        inlier_cloud = CL.statistical_outlier(pcd, nb_neighbors, std_ratio)
+        print(f"[Outlier] Keeping: {len(inlier_cloud)} pts")
+        if output_path:
+            ProcessingLogic._save_ply(*inlier_cloud.numpy(), output_path)
+            print(f"[Outlier] Saved to {output_path}")
+        return inlier_cloud if return_obj else None
+
+    @staticmethod
+    def remove_radius_outlier(input_data, output_path=None, nb_points=100, radius=5.0, return_obj=False):
+        """Radius outlier removal on the device (``server/processing.py:430-448``); the same two
+        differences from the reference as :meth:`remove_outliers`."""
+        from . import cloud as CL
+        print(f"[Radius Outlier] Processing...")
+        pcd = ProcessingLogic._load_pcd(input_data)
+        if not pcd.has_points():
+            raise ValueError("Point cloud is empty.")
+        inlier_cloud = CL.radius_outlier(pcd, nb_points, radius)
+        print(f"[Radius Outlier] Keeping: {len(inlier_cloud)} pts")
+        if output_path:
+            ProcessingLogic._save_ply(*inlier_cloud.numpy(), output_path)
+            print(f"[Radius Outlier] Saved to {output_path}")
+        return inlier_cloud if return_obj else None
 
 
 def batch_views() -> int:

@@ -1,0 +1,95 @@
+#!/usr/bin/env python
+"""Device cloud filters on one C2 view's cloud against the CPU restatement -- reported in
+DESIGN.md §9, never the bench metric.  One 1080p view (11+10 sets, Otsu) is reconstructed on the
+device (float64 XYZ); the radius filter and the statistical filter run on that device cloud at the
+reference's defaults, (nb_points 100, radius 5.0) and (nb_neighbors 20, std_ratio 2.0), timed with
+HIP events around mask + select (status and count are read once per call, as a user's call does).
+Beside that, the same rules on the host: tests/cloud_ref.py over scipy's cKDTree with
+``workers`` threads, on the same points, in the same run.  The two masks are compared.
+
+Prints one JSON line.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--row-mode", type=int, default=1)
+    ap.add_argument("--cam", type=int, nargs=2, default=(1920, 1080))
+    ap.add_argument("--workers", type=int, default=16)
+    ap.add_argument("--no-cpu", action="store_true", help="skip the cKDTree side")
+    args = ap.parse_args()
+
+    import numpy as np
+    import torch
+    from structured_light_for_3d_model_replication_amd import cloud as CL, engine as E, synth
+
+    assert torch.cuda.is_available(), "cloud_filter_bench needs a GPU"
+    W, H = args.cam
+    rig = synth.default_rig(W, H, 1920, 1080)
+    v = synth.render_view(rig, 25.0, seed=1, n_present=44)
+    frames = E.DeviceFrames(list(v.frames), v.texture)
+    eng = E.Reconstructor(H, W)
+    cfg = E.DecodeConfig(1920, 1080, 11, 10, "otsu")
+    dc = E.DeviceCalib(rig.tables(), H, W)
+    pc = CL.PointCloud.from_cloud(eng.reconstruct(frames, cfg, dc, row_mode=args.row_mode, xyz_f64=True))
+    n = len(pc)
+
+    def timed(fn):
+        ms = []
+        out = None
+        for i in range(args.warmup + args.steps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            out = fn()
+            b.record()
+            b.synchronize()
+            if i >= args.warmup:
+                ms.append(a.elapsed_time(b))
+        return out, ms
+
+    res = {"tool": "cloud_filter_bench", "points": n, "row_mode": args.row_mode, "cam": [W, H],
+           "steps": args.steps, "device": torch.cuda.get_device_name(0)}
+    (rad, rad_idx), ms = timed(lambda: CL.radius_outlier(pc, 100, 5.0, return_index=True))
+    res["radius"] = {"nb_points": 100, "radius": 5.0, "kept": len(rad), "device_ms": ms}
+    (_, counts), ms = timed(lambda: CL.radius_mask(pc.xyz, 100, 5.0))
+    res["radius"]["device_mask_only_ms"] = ms
+    res["radius"]["mean_candidates_in_radius"] = float(counts.double().mean().item())
+    (sta, sta_idx), ms = timed(lambda: CL.statistical_outlier(pc, 20, 2.0, return_index=True))
+    res["statistical"] = {"nb_neighbors": 20, "std_ratio": 2.0, "kept": len(sta), "device_ms": ms,
+                          "whole_cloud_points": CL.far_count(pc.xyz.device)}
+    _, ms = timed(lambda: CL.statistical_mask(pc.xyz, 20, 2.0))
+    res["statistical"]["device_mask_only_ms"] = ms
+
+    if not args.no_cpu:
+        import cloud_ref as R
+        P = pc.xyz.cpu().numpy()
+        t0 = time.perf_counter()
+        keep_r, _ = R.radius_filter(P, 100, 5.0, workers=args.workers)
+        t1 = time.perf_counter()
+        keep_s, _, _ = R.statistical_filter(P, 20, 2.0, workers=args.workers)
+        t2 = time.perf_counter()
+        res["cpu"] = {"what": f"tests/cloud_ref.py, scipy cKDTree(workers={args.workers})",
+                      "radius_ms": (t1 - t0) * 1e3, "statistical_ms": (t2 - t1) * 1e3}
+        res["radius"]["mask_equal_cpu"] = bool(np.array_equal(rad_idx.cpu().numpy(), np.flatnonzero(keep_r)))
+        res["statistical"]["mask_equal_cpu"] = bool(np.array_equal(sta_idx.cpu().numpy(), np.flatnonzero(keep_s)))
+        res["radius"]["speedup_vs_cpu"] = res["cpu"]["radius_ms"] / (sum(res["radius"]["device_ms"]) / args.steps)
+        res["statistical"]["speedup_vs_cpu"] = (res["cpu"]["statistical_ms"]
+                                                / (sum(res["statistical"]["device_ms"]) / args.steps))
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
