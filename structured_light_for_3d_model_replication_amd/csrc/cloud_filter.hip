@@ -30,9 +30,7 @@
 #include <rocprim/functional.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
-#include "../../include/slgpu.h"
-
-int slg_internal_fail(int code, const char* fmt, ...);
+#include "internal.h"
 
 namespace {
 
@@ -582,12 +580,6 @@ __global__ __launch_bounds__(256) void select_kernel(const double* __restrict__ 
 }
 
 // ---------------------------------------------------------------- host side
-int launch_ok(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return slg_internal_fail(SLG_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-  return SLG_OK;
-}
-
 int grid_of(int64_t n, int per) { return (int)((n + per - 1) / per); }
 
 struct Ws {
@@ -634,7 +626,7 @@ int build_grid(const double* xyz, int64_t n, const Ws& w, hipStream_t st) {
                               st) != hipSuccess)
     return slg_internal_fail(SLG_ERR_HIP, "cloud filter: scan failed");
   table_kernel<<<g, 256, 0, st>>>(n, w.hdr, w.keys_s, w.pos, w.ukeys, w.ustart);
-  return launch_ok("cloud filter grid build");
+  return check_launch("cloud filter grid build");
 }
 
 int bbox(const double* xyz, int64_t n, const Ws& w, double cell, int k, hipStream_t st) {
@@ -642,7 +634,7 @@ int bbox(const double* xyz, int64_t n, const Ws& w, double cell, int k, hipStrea
   const int nb = grid_of(n, kChunk);
   bbox_partial_kernel<<<nb, 256, 0, st>>>(xyz, n, w.hdr, w.part);
   bbox_final_kernel<<<1, 256, 0, st>>>(w.part, nb, w.hdr, cell, n, k);
-  return launch_ok("cloud filter bounding box");
+  return check_launch("cloud filter bounding box");
 }
 
 constexpr int64_t kMaxPoints = 1ll << 30;    // 32-bit sorted indices and offsets
@@ -678,7 +670,7 @@ int32_t slg_radius_outlier(const double* xyz, int64_t n, double radius, int32_t 
   const int64_t g = n < 8192 ? n : 8192;
   radius_count_kernel<<<(int)g, 256, 0, st>>>(w.hdr, w.sxyz, w.idx_s, w.ukeys, w.ustart, radius * radius, nb_points,
                                               keep_out, counts_out);
-  return launch_ok("radius_count_kernel");
+  return check_launch("radius_count_kernel");
 }
 
 int32_t slg_statistical_outlier(const double* xyz, int64_t n, int32_t nb_neighbors, double std_ratio, void* ws,
@@ -709,7 +701,7 @@ int32_t slg_statistical_outlier(const double* xyz, int64_t n, int32_t nb_neighbo
   sum_partial_kernel<1><<<nb, 256, 0, st>>>(w.hdr, avg, n, w.part);
   sum_final_kernel<1><<<1, 256, 0, st>>>(w.hdr, w.part, nb, n, std_ratio, stats_out);
   stat_keep_kernel<<<grid_of(n, 256), 256, 0, st>>>(w.hdr, avg, n, keep_out);
-  return launch_ok("slg_statistical_outlier");
+  return check_launch("slg_statistical_outlier");
 }
 
 int32_t slg_cloud_select(const double* xyz, const uint8_t* bgr, int64_t n, const uint8_t* keep, const slg_cloud* out,
@@ -727,7 +719,7 @@ int32_t slg_cloud_select(const double* xyz, const uint8_t* bgr, int64_t n, const
     return slg_internal_fail(SLG_ERR_HIP, "slg_cloud_select: scan failed");
   select_kernel<<<grid_of(n, 256), 256, 0, st>>>(xyz, bgr, n, keep, w.pos, (double*)out->xyz, out->bgr, out->count,
                                                 out->capacity, index_out);
-  return launch_ok("select_kernel");
+  return check_launch("select_kernel");
 }
 
 }  // extern "C"

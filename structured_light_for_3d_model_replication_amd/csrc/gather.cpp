@@ -19,9 +19,7 @@
 
 #include <vector>
 
-#include "../../include/slgpu.h"
-
-int slg_internal_fail(int code, const char* fmt, ...);   // slgpu.hip: sets slg_last_error()
+#include "internal.h"
 
 namespace {
 

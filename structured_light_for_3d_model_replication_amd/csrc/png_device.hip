@@ -22,9 +22,7 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
-#include "../../include/slgpu.h"
-
-int slg_internal_fail(int code, const char* fmt, ...);
+#include "internal.h"
 
 namespace {
 

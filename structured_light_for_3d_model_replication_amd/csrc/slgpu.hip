@@ -1,13 +1,21 @@
-// slgpu.hip — MI355X (gfx950, CDNA4) kernels for the structured-light hot path.
+// slgpu.hip -- the structured-light hot path on MI355X (gfx950, CDNA4): mask thresholds, the
+// fused decode + triangulate kernel, their launch code and the C ABI entries that run them.
 //
 // Path (reference): Gray-code decode  server/processing.py:28-124, server/sl_system.py:516-588
 //                   ray-plane triangulation  server/processing.py:127-234, sl_system.py:592-661
 // C ABI: include/slgpu.h.  Design and rooflines: DESIGN.md.
 //
-// Kernels
+// Beside this file: workspace.h (the per-view workspace layout), otsu.h (histogram / Otsu /
+// percentile device code the kernels below share), internal.h (last-error entry, launch check),
+// code_object.cpp (which kernels the built library carries), ply.hip (PLY text), color_gray.hip
+// (colour ingest), png_device.hip, png_gray.cpp, cloud_filter.hip, gather.cpp.
+//
+// Kernels here
 //   stats_kernel      white/black histograms (+ max contrast) -> last-arriving workgroup turns
 //                     them into integer mask thresholds (Otsu as OpenCV, or NumPy percentile);
 //                     also zeroes the compaction state of the next main launch.
+//   parts_kernel, hist_thresholds_kernel  the same thresholds from per-tile partial histograms a
+//                     fused launch carried, or from histograms summed over the ranks' bands.
 //   main3_kernel<...> fused decode + triangulate + ordered compaction, one 4096-pixel tile per
 //                     workgroup (512 lanes x 8 pixels), up to 16 views per launch: the mask
 //                     first (white/black), then the used pattern frames only in lanes holding a
@@ -19,7 +27,10 @@
 //                     can turn a carried batch's Otsu partials into thresholds.
 //   decode_maps_kernel  the decode alone, to correspondence maps (slg_decode).
 //   row_tail_kernel   row_mode 2: moves the row cloud behind the column cloud.
+//   set_arena_kernel  the resident-job arena words of the workspace headers.
 //   pinhole_kernel    bitwise Nc == pinhole(cam_K) test.
+// Host side: argument checks and the decode plan, the main3 instance table (pick_main refuses an
+// instance the library's code object lacks), the batched launch code, the C ABI.
 //
 // Numerics: every floating-point expression follows NumPy's operation order with
 // -ffp-contract=off (no FMA contraction), IEEE-correct f64 division and sqrt, so the fp64
@@ -36,83 +47,25 @@
 #include <stdlib.h>
 #include <math.h>
 #include <string>
-#include <errno.h>
-#include <fcntl.h>
-#include <unistd.h>
-#include <thread>
 #include <vector>
 #include <algorithm>
 #include <mutex>
 #include <dlfcn.h>
 
-#include "../../include/slgpu.h"
+#include "code_object.h"
+#include "internal.h"
+#include "otsu.h"
+#include "workspace.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kBlock = 256;                 // 4 waves of 64
-constexpr int kPx = 8;                      // pixels per lane (one 8-byte load per frame)
-#ifndef SLG_TILE_BLOCK
-#define SLG_TILE_BLOCK 512
-#endif
-constexpr int kTileBlock = SLG_TILE_BLOCK;  // main3 workgroup: 512 lanes, 322.6 vs 331.3 us per
-                                            // 12-view launch with 256 (half the look-backs per pixel)
-constexpr int kTilePx = kTileBlock * kPx;   // 4096 pixels per main3 tile (one look-back entry)
 constexpr int kMapsPx = kBlock * kPx;       // 2048 pixels per decode_maps workgroup
 constexpr int kMaxBits = 15;                // packed 16-bit code lanes
 constexpr uint64_t kFlagAgg = 1ull << 62;
 constexpr uint64_t kFlagInc = 2ull << 62;
 constexpr uint64_t kValMask = (1ull << 62) - 1;
-
-// ------------------------------------------------------------------ workspace layout
-struct WsHeader {
-  uint32_t hist[3][256];   // otsu: 0 white, 1 clip(white-black,0,255); percentile: 0 black
-  uint32_t max_diff_enc;   // max(white-black) + 256 (0 = none yet)
-  uint32_t ticket;         // stats_kernel arrival counter
-  uint32_t lb_ticket;      // main3 tiles that published their column-stream aggregate (lookback_scan)
-  uint32_t error;          // bit 0: look-back spin timeout; 1: a look-back helper ran
-  int32_t smin;            // mask: white >= smin
-  int32_t cmin;            //       (white - black) >= cmin
-  uint32_t lb_ticket_row;  // the same for the row stream (row_mode 2)
-  int32_t pad0;
-  double thr_s;            // float thresholds (for inspection / tests)
-  double thr_c;
-  int64_t totals[2];       // column / row stream point totals
-  // Otsu only: pixels with white >= smin, and with white - black >= cmin (n_px when cmin <= 0,
-  // which the clipped histogram cannot count); their minimum bounds the valid pixels, so the
-  // point count of row_mode 0/1 (resident jobs size their clouds with it).  n_px otherwise.
-  int64_t above[2];
-  // Resident-job arena (slg_workspace_set_arena; NULL cursor: none).  The Otsu tail that sets a
-  // view's thresholds also reserves its cloud's region: arena_off = atomicAdd(cursor, need),
-  // need = min(above) * arena_mult (an upper bound of its points), or -1 when the arena has no
-  // room left (the fused launch then stores nothing for it; the host re-runs it).
-  int64_t arena_off;
-  int32_t arena_mult;      // points per valid pixel at most: 1 (row_mode 0/1) or 2 (row_mode 2)
-  int32_t pad4;
-  unsigned long long* arena_cursor;
-  int64_t arena_cap;       // points the arena holds
-  uint64_t pad3[2];
-};
-constexpr int kHistCopies = 16;            // partial histograms: blocks spread their atomics
-constexpr int64_t kHistPartOff = 8192;      // uint32 [kHistCopies][2][256] after the header
-constexpr int64_t kHeaderBytes = 65536;
-static_assert(sizeof(WsHeader) <= kHistPartOff, "header");
-static_assert(offsetof(WsHeader, error) == 3084 && offsetof(WsHeader, totals) == 3120 && offsetof(WsHeader, above) == 3136 &&
-              offsetof(WsHeader, arena_off) == 3152,
-              "header offsets the host reads (engine.py: error word, WS_TOTALS_OFF, WS_ABOVE_OFF)");
-
-__host__ __device__ inline int64_t n_tiles_of(int64_t n_px) { return (n_px + kTilePx - 1) / kTilePx; }
-__host__ __device__ inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-__host__ __device__ inline int64_t states_off(int64_t) { return kHeaderBytes; }
-__host__ __device__ inline int64_t n_state_words(int64_t n_px) { return 2 * n_tiles_of(n_px); }   // [stream][tile]
-__host__ __device__ inline int64_t states_bytes(int64_t n_px) { return align_up(n_state_words(n_px) * 8, 256); }
-__host__ __device__ inline int64_t scratch_xyz_off(int64_t n_px) { return kHeaderBytes + states_bytes(n_px); }
-__host__ __device__ inline int64_t scratch_bgr_off(int64_t n_px) { return scratch_xyz_off(n_px) + align_up(n_px * 24, 256); }
-__host__ __device__ inline int64_t parts_off(int64_t n_px) { return scratch_bgr_off(n_px) + align_up(n_px * 3, 256); }
-// per tile: the Otsu histograms of the batch after next over the tile's pixels, u16 [2][256]
-constexpr int64_t kPartWords = 256;         // packed u16 pairs per tile
-__host__ __device__ inline int64_t ws_total(int64_t n_px) { return parts_off(n_px) + align_up(n_tiles_of(n_px) * kPartWords * 4, 256); }
 
 // ------------------------------------------------------------------ small helpers
 __device__ inline uint64_t ld_state(const uint64_t* p) {
@@ -125,32 +78,6 @@ __device__ inline void st_state(uint64_t* p, uint64_t v) {
 #ifndef SLG_FRAME_BUFFER_LOADS
 #define SLG_FRAME_BUFFER_LOADS 1           // frame loads as buffer loads (scalar base, 32-bit lane offset)
 #endif
-#ifndef SLG_NT_LOADS
-#define SLG_NT_LOADS 1                     // frames / texture are read once: non-temporal loads
-#endif
-// Once-read stream (frames, texture): non-temporal 8-byte load (global_load_dwordx2 nt).
-typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
-__device__ inline uint2 ld_once8(const void* ptr) {
-#if SLG_NT_LOADS
-  const u32x2_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x2_t*>(ptr));
-  return make_uint2(v.x, v.y);
-#else
-  return *reinterpret_cast<const uint2*>(ptr);
-#endif
-}
-
-template <class T>
-__device__ inline T wave_sum(T x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
-__device__ inline int wave_min_i(int x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x = min(x, __shfl_xor(x, o));
-  return x;
-}
-
 // Per-byte unsigned p > i on 4 packed bytes: 0x80 in every byte lane where p > i.
 __device__ inline uint32_t gt_u8x4(uint32_t p, uint32_t i) {
   // per byte p > i in bit 7 (other bits garbage: callers mask with 0x80808080):
@@ -204,500 +131,9 @@ struct StatsParams {
   uint32_t* hist_out;                 // one view, histograms only (slg_decode_histograms): no thresholds
 };
 
-// a / b correctly rounded from y = RN(1/b) (Markstein): with y correctly rounded and q1
-// faithful, q2 = RN(q1 + (a - b*q1) * y) = RN(a / b); q0 = RN(a*y) is within 1.5 ulp, so one
-// correction makes q1 faithful and the second one is exact (tools/markstein_check.c checks it
-// against IEEE division).  Valid while nothing over/underflows: div_rn_ok() vets a, the
-// caller vets b and y.
-__device__ inline double div_rn(double a, double b, double y) {
-  const double q0 = a * y;
-  const double q1 = fma(fma(-b, q0, a), y, q0);
-  return fma(fma(-b, q1, a), y, q1);
-}
-__device__ inline bool div_rn_ok(double a) {
-  const double m = fabs(a);
-  return m == 0.0 || (m > 0x1p-900 && m < 0x1p900);
-}
-
-// OpenCV getThreshVal_Otsu_8u (see oracle/sl_oracle.py:otsu_from_hist) evaluated by one wave.
-// Bit-exact with the sequential fp64 loop: only order-independent pieces run in parallel.
-//  * mu = sum(i*h[i]) of exact integers (< 2^53) == OpenCV's sequential double sum;
-//  * q1 (running sum of p_i = h[i]*scale) is one sequential add chain (same rounding as the
-//    loop); it alone decides which bins OpenCV skips, so the skip flags, i*p_i and
-//    y = RN(1/q1) are then computed lane-parallel, bin i on lane i/4;
-//  * the remaining chain mu1 = (mu1*q1_prev + i*p_i)/q1 runs on wave-uniform registers up to
-//    the last unskipped bin, each division as the Markstein pair div_rn(., q1, y) (IEEE
-//    division when div_rn_ok refuses the numerator): 7 dependent fp64 ops per bin instead of a
-//    full IEEE division sequence;
-//  * sigma per bin and the first-maximum argmax (strict '>' from 0) are lane-parallel.
-__device__ inline double readlane_f64(double v, int l) {
-  const uint64_t b = uint64_t(__double_as_longlong(v));
-  const uint32_t lo = __builtin_amdgcn_readlane(uint32_t(b), l);
-  const uint32_t hi = __builtin_amdgcn_readlane(uint32_t(b >> 32), l);
-  return __longlong_as_double((long long)((uint64_t(hi) << 32) | lo));
-}
-
-// otsu_wave's exact mu1 run over bins [lo, hi] (the rerun when the speculative chain misses):
-// each quotient as the Markstein pair div_rn(a, q1, y).
-__device__ inline void mu1_run_exact(int lo, int hi, const double (&ip)[4], const double (&q1r)[4],
-                                     const double (&yr)[4], double (&m1r)[4]) {
-  const int lane = threadIdx.x & 63;
-  double mu1 = 0.0, q_prev = 0.0;                    // bin i's previous q1 is bin i-1's q1 (mu1 = 0 at lo)
-  for (int l = lo >> 2; l <= (hi >> 2); ++l) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int i = 4 * l + j;
-      if (i < lo || i > hi) continue;                // scalar: first and last lane only
-      const double a = mu1 * q_prev + readlane_f64(ip[j], l);
-      q_prev = readlane_f64(q1r[j], l);
-      mu1 = div_rn(a, q_prev, readlane_f64(yr[j], l));
-      if (lane == l) m1r[j] = mu1;
-    }
-  }
-}
-
-// Pixels of a 256-bin histogram at or above bin m (the wave's sum).  n when m <= 0: the clipped
-// difference histogram puts every negative white - black into bin 0, so it cannot tell which of
-// them reach a threshold below 1 (for white, m <= 0 is every pixel anyway).
-__device__ __attribute__((always_inline)) inline int64_t hist_at_least_wave(const uint32_t* h, int m, int64_t n) {
-  if (m <= 0) return n;
-  const int lane = threadIdx.x & 63;
-  uint64_t a = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int b = 64 * j + lane;
-    if (b >= m) a += h[b];
-  }
-  return int64_t(wave_sum(a));
-}
-
-// The resident-job arena reservation of one view, by the thread that finishes its thresholds,
-// from its two `above` counts: see WsHeader::arena_off.
-__device__ inline void arena_reserve(WsHeader* ws, int64_t a0, int64_t a1) {
-  unsigned long long* cur = ws->arena_cursor;
-  if (!cur) return;
-  const int64_t need = (a0 < a1 ? a0 : a1) * int64_t(ws->arena_mult);
-  const int64_t off = int64_t(atomicAdd(cur, (unsigned long long)need));
-  ws->arena_off = off + need <= ws->arena_cap ? off : -1;
-}
-
-// The two serial chains of otsu_wave (q1, then mu1) run on wave-uniform registers fed from LDS:
-// every lane computes the same chain, its per-bin operands read as broadcast LDS words, and only
-// the value after each lane's four bins is captured (one 64-bit select per four steps); each
-// lane then redoes its own four steps from its left neighbour's capture -- the same operations on
-// the same values in the same order, so the same bits.  A dependent fp64 op costs ~5 clocks
-// (tools/dp_latency_probe.hip), so a step costs its instruction count (profiles/r5y: 7.8 us for
-// one 1080p histogram).  lds: kOtsuLds doubles of this wave's own.
-#ifndef SLG_OTSU_MARK
-#define SLG_OTSU_MARK(k)                   // tools/otsu_probe.hip: a timestamp per part of otsu_wave
-#endif
-#ifndef SLG_OTSU_UNROLL
-#define SLG_OTSU_UNROLL 2                  // the chain loops: steps per loop body
-#endif
-constexpr int kOtsuLds = 5 * 256;          // p_i [256] + the mu1 chain's {q1[i-1], ip, y, c} [256][4]
-
-__device__ __attribute__((always_inline)) inline double otsu_wave(const uint32_t* h, int64_t n, double* lds) {
-  SLG_OTSU_MARK(0);
-  const int lane = threadIdx.x & 63;
-  const double scale = 1.0 / double(n);
-  const double eps = double(__FLT_EPSILON__);
-  double* sp = lds;                 // p_i
-  double pv[4], ip[4], q1r[4], yr[4], m1r[4], ar[4];
-  uint64_t isum = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int i = 4 * lane + j;
-    pv[j] = double(h[i]) * scale;
-    ip[j] = double(i) * pv[j];
-    isum += uint64_t(i) * h[i];
-    q1r[j] = yr[j] = m1r[j] = ar[j] = 0.0;
-    sp[i] = pv[j];
-  }
-  isum = wave_sum(isum);
-  const double mu = double(isum) * scale;
-  SLG_OTSU_MARK(1);
-  // 1. the q1 chain (OpenCV's order) from broadcast LDS reads (wave-local: the wave's own LDS ops
-  // are in order, the fence only keeps the compiler from moving them)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  {
-    double q1 = 0.0, qcap = 0.0;
-#pragma unroll SLG_OTSU_UNROLL
-    for (int l0 = 0; l0 < 64; l0 += 4) {
-      double pp[16];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) pp[k] = sp[4 * l0 + k];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) q1 = q1 + pp[4 * t + j];
-        qcap = lane == l0 + t ? q1 : qcap;
-      }
-    }
-    double q = __shfl_up(qcap, 1);
-    if (lane == 0) q = 0.0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      q = q + pv[j];
-      q1r[j] = q;
-    }
-  }
-  SLG_OTSU_MARK(2);
-  uint32_t okr = 0;                                  // 2. bit j: bin 4*lane+j not skipped
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const double q2 = 1.0 - q1r[j];
-    if (!(fmin(q1r[j], q2) < eps || fmax(q1r[j], q2) > 1.0 - eps)) {
-      okr |= 1u << j;
-      yr[j] = 1.0 / q1r[j];
-    }
-  }
-  // 3. the mu1 chain.  The unskipped bins form one run [lo, hi]: q1 never decreases and
-  // q2 = RN(1 - q1) never increases, so each skip test holds on a prefix plus a suffix of the
-  // bins, and mu1 is still 0 at lo.  Over the run every bin is the same few dependent ops,
-  // each quotient taken speculatively as fma(a, y, a * c) with c = fma(-q1, y, 1) * y (y + c
-  // is 1/q1 to ~2^-105): faithful, and RN(a / q1) unless a / q1 sits within ~2^-105 of a
-  // rounding boundary -- so every bin is checked afterwards (Markstein: RN(m + (a - q1 m) y)
-  // = RN(a / q1) for faithful m) and the run is redone exactly on a miss.  That needs every
-  // numerator to suit div_rn: a is 0, or at least ~1/n (an empty bin's mu1 *= q1 then / q1
-  // moves a by ulps), so n <= 2^52 keeps a far inside its range.  Anything else (never seen)
-  // takes the general loop: per-bin skip flags, IEEE division when refused.
-  SLG_OTSU_MARK(3);
-  const uint64_t lanes_ok = __ballot(okr != 0);
-  int lo = 256, hi = -1, n_ok = 0;
-  if (lanes_ok) {
-    const int l_lo = __builtin_ctzll(lanes_ok), l_hi = 63 - __builtin_clzll(lanes_ok);
-    lo = 4 * l_lo + __builtin_ctz(__builtin_amdgcn_readlane(okr, l_lo));
-    hi = 4 * l_hi + 31 - __builtin_clz(__builtin_amdgcn_readlane(okr, l_hi));
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) n_ok += __popcll(__ballot((okr >> j) & 1u));
-  double mu1 = 0.0;
-  SLG_OTSU_MARK(4);
-  if (n_ok == hi - lo + 1 && n <= (int64_t(1) << 52)) {
-    {                                                // per bin {q1[i-1], ip, y, c}, 32 bytes
-      double* sops = lds + 256;
-      const double qprev0 = __shfl_up(q1r[3], 1);
-      double cr[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        double* o = sops + 4 * (4 * lane + j);
-        cr[j] = fma(-q1r[j], yr[j], 1.0) * yr[j];
-        o[0] = j == 0 ? qprev0 : q1r[j - 1];
-        o[1] = ip[j];
-        o[2] = yr[j];
-        o[3] = cr[j];
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      // the chain over [lo, hi] (mu1 is 0 at lo, whatever q1[lo-1]), one capture per 4 bins:
-      // mcap of lane l = mu1 after bin min(4l + 3, hi)
-      double mu1c = 0.0, mcap = 0.0;
-      const int g_lo = lo >> 2, g_hi = hi >> 2;
-      // the edge groups (partial) apart, so the middle ones are one straight-line body the
-      // scheduler can unroll and issue the next group's LDS reads ahead in (an explicitly
-      // double-buffered form measured no faster: the buffers were shuffled through extra
-      // registers, profiles/r5x)
-      auto edge = [&](int l) {
-        double o[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) o[k] = sops[16 * l + k];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int i = 4 * l + j;
-          if (i >= lo && i <= hi) {                  // (wave-uniform)
-            const double a = mu1c * o[4 * j] + o[4 * j + 1];
-            mu1c = fma(a, o[4 * j + 2], a * o[4 * j + 3]);
-          }
-        }
-        mcap = lane == l ? mu1c : mcap;
-      };
-      edge(g_lo);
-#pragma unroll SLG_OTSU_UNROLL
-      for (int l = g_lo + 1; l < g_hi; ++l) {
-        double o[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) o[k] = sops[16 * l + k];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const double a = mu1c * o[4 * j] + o[4 * j + 1];
-          mu1c = fma(a, o[4 * j + 2], a * o[4 * j + 3]);
-        }
-        mcap = lane == l ? mu1c : mcap;
-      }
-      if (g_hi > g_lo) edge(g_hi);
-      // every lane redoes its own bins from its left neighbour's capture (0 before g_lo)
-      double m = __shfl_up(mcap, 1);
-      if (lane <= g_lo) m = 0.0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int i = 4 * lane + j;
-        const double qp = j == 0 ? qprev0 : q1r[j - 1];
-        const double a = m * qp + ip[j];
-        const double mj = fma(a, yr[j], a * cr[j]);
-        if (i >= lo && i <= hi) {
-          m = mj;
-          m1r[j] = mj;
-          ar[j] = a;
-        }
-      }
-    }
-    SLG_OTSU_MARK(5);
-    uint32_t miss = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const double r = fma(-q1r[j], m1r[j], ar[j]);   // exact remainder
-      if ((okr >> j) & 1u) miss |= uint32_t(fma(r, yr[j], m1r[j]) != m1r[j]);
-    }
-    if (__ballot(miss != 0)) mu1_run_exact(lo, hi, ip, q1r, yr, m1r);
-  } else {
-    const int l_end = 64 - __builtin_clzll(lanes_ok | 1ull);   // lanes with work: [0, l_end)
-    double q_prev = 0.0;
-    for (int l = 0; l < l_end; ++l) {
-      const uint32_t okl = __builtin_amdgcn_readlane(okr, l);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        mu1 *= q_prev;                               // mu1 *= q1 (previous q1)
-        const double q = readlane_f64(q1r[j], l);
-        if (okl & (1u << j)) {
-          const double a = mu1 + readlane_f64(ip[j], l);
-          mu1 = div_rn_ok(a) ? div_rn(a, q, readlane_f64(yr[j], l)) : a / q;
-          if (lane == l) m1r[j] = mu1;
-        }
-        q_prev = q;
-      }
-    }
-  }
-  SLG_OTSU_MARK(6);
-  double best = 0.0;
-  int best_i = INT_MAX;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (!(okr & (1u << j))) continue;
-    const double q1j = q1r[j], q2 = 1.0 - q1j, mu1j = m1r[j];
-    const double mu2 = (mu - q1j * mu1j) / q2;
-    const double sigma = q1j * q2 * (mu1j - mu2) * (mu1j - mu2);
-    if (sigma > best) { best = sigma; best_i = 4 * lane + j; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ob = __shfl_xor(best, o);
-    const int oi = __shfl_xor(best_i, o);
-    if (ob > best || (ob == best && oi < best_i)) { best = ob; best_i = oi; }
-  }
-  SLG_OTSU_MARK(7);
-  return best_i == INT_MAX ? 0.0 : double(best_i);
-}
-
-// smallest integer x in [lo, 256] with double(x) > thr (256 = none reachable)
-__device__ inline int int_threshold(double thr, int lo) {
-  if (!(thr == thr)) return 256;                 // NaN: comparison always false
-  if (thr < double(lo)) return lo;
-  if (thr >= 256.0) return 256;
-  return int(floor(thr)) + 1;
-}
-
-// k-th smallest value (0-based) from a 256-bin histogram.
-__device__ __attribute__((always_inline)) inline int kth_from_hist(const uint32_t* h, int64_t k) {
-  int64_t c = 0;
-  for (int v = 0; v < 256; ++v) {
-    c += h[v];
-    if (c > k) return v;
-  }
-  return 255;
-}
-
-// np.percentile(float32 image, 95) with method 'linear' (numpy 2.x _quantile/_lerp, float32).
-__device__ __attribute__((always_inline)) inline float percentile95_from_hist(const uint32_t* h, int64_t n) {
-  const float q = 95.0f / 100.0f;                       // np.true_divide(95, float32(100))
-  const float vi = float(n - 1) * q;                    // (n-1) * quantiles, float32
-  float prev = floorf(vi);
-  float next = prev + 1.0f;
-  const float gamma = vi - prev;
-  int64_t pi = int64_t(prev), ni = int64_t(next);
-  if (vi >= float(n - 1)) { pi = n - 1; ni = n - 1; }   // index -1 -> last element
-  const float a = float(kth_from_hist(h, pi));
-  const float b = float(kth_from_hist(h, ni));
-  const float diff = b - a;
-  float r = a + diff * gamma;
-  if (gamma >= 0.5f) r = b - diff * (1.0f - gamma);
-  return r;
-}
-
-// ---- Otsu histograms on the i8 matrix cores.  For 64 pixels v_k (k = 16 * lane-group + byte),
-// A[m][k] = 16 * [v_k >> 4 == m] and B[k][n] = 16 * [v_k & 15 == n], so one
-// v_mfma_i32_16x16x64_i8 adds 256 x the count of every value v = 16m + n: no LDS atomics (which
-// retire about one lane per clock).  The 16 lanes of a row group (lane >> 4) hold the same 16
-// pixels, each against its own m or n = lane & 15.  Operand dwords are built in two VALU ops:
-// ((nib ^ (m ^ 15)) + 1) & 0x10 = 16 - (nib ^ m) masked to bit 4, i.e. 0x10 iff nib == m (no
-// carries between bytes: every byte stays in 1..16).  Lane maps checked by
-// tools/mfma_hist_probe.hip; C/D: col = lane & 15, row = 4 * (lane >> 4) + r.
-//
-// main3's carried count (hist_next_count: other waves' pixels) stages nibble planes in LDS and
-// reads them with broadcast ds_read_b128.  stats_kernel counts each wave's own pixels
-// (hist_chunk_dpp): MFMA step i takes row group g's pixels from lane 16 g + i by a DPP
-// row_newbcast folded into the operand's add, so no LDS at all -- the LDS form read 4 KB per wave
-// and step through the CU's LDS port, four waves per CU, which bounded the count.  The folded
-// add cannot also take the xor, so those operands are step functions, 0x10 iff nib >= m
-// ((nib + 16 - m) & 0x10), the MFMA sums S[m][n] = #{hi >= m, lo >= n}, and the wave's
-// histogram is the 2-D difference S[m][n] - S[m+1][n] - S[m][n+1] + S[m+1][n+1] taken once on
-// the accumulators (hist_from_cumulative).
-typedef int v4i32 __attribute__((ext_vector_type(4)));
-constexpr int kHistChunk = 1024;            // pixels per wave and MFMA chunk (16 per lane)
-constexpr int64_t kHistMaxChunks = 8000;    // per wave: 8000 * 1024 * 256 < 2^31 (i32 accumulators)
-
-__device__ inline uint32_t sub_sat_u8x4(uint32_t w, uint32_t b) {   // per byte max(w - b, 0)
-  const uint32_t dl = ((w & 0x00ff00ffu) | 0x01000100u) - (b & 0x00ff00ffu);   // 256 + w - b
-  const uint32_t dh = (((w >> 8) & 0x00ff00ffu) | 0x01000100u) - ((b >> 8) & 0x00ff00ffu);
-  const uint32_t ml = ((dl >> 8) & 0x00010001u) * 0xffu, mh = ((dh >> 8) & 0x00010001u) * 0xffu;
-  return (dl & ml) | ((dh & mh) << 8);
-}
-
-__device__ inline int onehot16(uint32_t nib, uint32_t repx) {      // bytes: 0x10 iff nib == m
-  return int(((nib ^ repx) + 0x01010101u) & 0x10101010u);
-}
-
-// Step I of a chunk: per byte 0x10 iff the nibble of lane 16 * (lane >> 4) + I >= m, where
-// c = (16 - m) per byte, m = lane & 15.  Bytes stay in 1..31: no carries.
-template <int I>
-__device__ inline int ge16_bcast(uint32_t plane, uint32_t c) {
-  const uint32_t b = uint32_t(__builtin_amdgcn_update_dpp(0, int(plane), 0x150 + I, 0xf, 0xf, false));  // row_newbcast:I
-  return int((b + c) & 0x10101010u);
-}
-
-// pl: the lane's 16 pixels as nibble planes {hi(w)[4], lo(w)[4], hi(d)[4], lo(d)[4]}
-template <int I>
-__device__ inline void hist_step_dpp(const uint32_t (&pl)[16], uint32_t c, v4i32& acc_w, v4i32& acc_d) {
-  const v4i32 aw = {ge16_bcast<I>(pl[0], c), ge16_bcast<I>(pl[1], c), ge16_bcast<I>(pl[2], c), ge16_bcast<I>(pl[3], c)};
-  const v4i32 bw = {ge16_bcast<I>(pl[4], c), ge16_bcast<I>(pl[5], c), ge16_bcast<I>(pl[6], c), ge16_bcast<I>(pl[7], c)};
-  const v4i32 ad = {ge16_bcast<I>(pl[8], c), ge16_bcast<I>(pl[9], c), ge16_bcast<I>(pl[10], c), ge16_bcast<I>(pl[11], c)};
-  const v4i32 bd = {ge16_bcast<I>(pl[12], c), ge16_bcast<I>(pl[13], c), ge16_bcast<I>(pl[14], c), ge16_bcast<I>(pl[15], c)};
-  acc_w = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw, bw, acc_w, 0, 0, 0);
-  acc_d = __builtin_amdgcn_mfma_i32_16x16x64_i8(ad, bd, acc_d, 0, 0, 0);
-}
-
-template <int... Is>
-__device__ inline void hist_steps_dpp(std::integer_sequence<int, Is...>, const uint32_t (&pl)[16], uint32_t c,
-                                      v4i32& acc_w, v4i32& acc_d) {
-  (hist_step_dpp<Is>(pl, c, acc_w, acc_d), ...);
-}
-
-// One wave adds its 1024 pixels (pixel c + 16 * lane + byte: white w[], clip(white - black) d[])
-// into its cumulative accumulators S_w, S_d (256 x #{hi >= m, lo >= n}).
-__device__ inline void hist_chunk_dpp(const uint32_t (&w)[4], const uint32_t (&d)[4], v4i32& acc_w, v4i32& acc_d) {
-  const uint32_t m4 = 0x0f0f0f0fu;
-  const uint32_t c = (16u - uint32_t(threadIdx.x & 15)) * 0x01010101u;
-  uint32_t pl[16];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    pl[q] = (w[q] >> 4) & m4; pl[4 + q] = w[q] & m4;
-    pl[8 + q] = (d[q] >> 4) & m4; pl[12 + q] = d[q] & m4;
-  }
-  hist_steps_dpp(std::make_integer_sequence<int, 16>(), pl, c, acc_w, acc_d);
-}
-
-// S (this lane's C/D entries: row 4 * (lane >> 4) + r, col lane & 15) -> the histogram entries
-// S[m][n] - S[m+1][n] - S[m][n+1] + S[m+1][n+1], S past row / column 15 being 0.
-__device__ inline v4i32 hist_from_cumulative(v4i32 s) {
-  const int lane = threadIdx.x & 63;
-  const int below = __shfl_down(s[0], 16);        // row 4 * (g + 1): lane + 16, same column
-  v4i32 dm;
-  dm[0] = s[0] - s[1]; dm[1] = s[1] - s[2]; dm[2] = s[2] - s[3]; dm[3] = s[3] - (lane < 48 ? below : 0);
-  v4i32 h;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int right = __shfl_down(dm[r], 1);       // column n + 1: lane + 1
-    h[r] = dm[r] - ((lane & 15) != 15 ? right : 0);
-  }
-  return h;
-}
-
-// 16 pixels of white and clip(white - black) for lane `lane` of the chunk at c; bytes at or
-// past n_px read as 0 (the last arriver removes them from bin 0).
-__device__ inline void hist_load(const uint8_t* white, const uint8_t* black, int64_t c, int64_t n_px,
-                                 uint32_t (&w)[4], uint32_t (&d)[4]) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {             // two 8-byte loads
-    const int64_t o = c + 16 * lane + 8 * h;
-    const int64_t so = o < n_px ? o : 0;    // frames readable to round_up(n, 8)
-    uint2 wq = ld_once8(white + so);
-    uint2 bq = ld_once8(black + so);
-    if (o + 8 > n_px) {                     // tail: zero the bytes at or past n_px
-      const int64_t keep = n_px - o;        // <= 0: none
-      const uint64_t mk = keep <= 0 ? 0 : (~0ull >> (64 - 8 * keep));
-      wq.x &= uint32_t(mk); wq.y &= uint32_t(mk >> 32);
-      bq.x &= uint32_t(mk); bq.y &= uint32_t(mk >> 32);
-    }
-    w[2 * h] = wq.x; w[2 * h + 1] = wq.y;
-    d[2 * h] = sub_sat_u8x4(wq.x, bq.x); d[2 * h + 1] = sub_sat_u8x4(wq.y, bq.y);
-  }
-}
-
-// The mask thresholds of a view from its summed histograms into ws (stats_kernel's last arriver,
-// hist_thresholds_kernel): Otsu of hg[0..255] (white) and hg[256..511] (clip(white - black)) by
-// waves 0 and 1 concurrently, with the bound of the valid pixels (WsHeader::above); or the
-// percentile rule from hg[0..255] (black) and maxd = max(white - black) + 256.  otsu_lds: two
-// waves' kOtsuLds doubles.  Then the resident-job arena reservation (no cursor: nothing).
-__device__ __attribute__((always_inline)) inline void set_thresholds(const uint32_t* hg, uint32_t maxd, int64_t n_px,
-                                                                     bool otsu, WsHeader* ws, double* otsu_lds,
-                                                                     int64_t* s_above) {
-  const int tid = threadIdx.x, wave = tid >> 6;
-  if (otsu) {
-    if (wave < 2) {                            // wave 0: white, wave 1: clip(w-b); concurrently
-      const double thr = otsu_wave(hg + 256 * wave, n_px, otsu_lds + wave * kOtsuLds);
-      const int m = int_threshold(thr, wave == 0 ? 0 : -255);
-      const int64_t above = hist_at_least_wave(hg + 256 * wave, m, n_px);
-      if ((tid & 63) == 0) {
-        if (wave == 0) { ws->smin = m; ws->thr_s = thr; } else { ws->cmin = m; ws->thr_c = thr; }
-        ws->above[wave] = above;
-        s_above[wave] = above;
-      }
-    }
-  } else if (tid < 2) {
-    double thr;
-    if (tid == 0) {
-      const float nf = percentile95_from_hist(hg, n_px);
-      thr = double(nf * 1.5f);                           // noise_floor * 1.5 (float32)
-    } else {
-      const float dr = float(int(maxd) - 256);           // np.max(contrast)
-      thr = double(dr * 0.05f);                          // dynamic_range * 0.05 (float32)
-    }
-    const int m = int_threshold(thr, tid == 0 ? 0 : -255);
-    if (tid == 0) { ws->smin = m; ws->thr_s = thr; } else { ws->cmin = m; ws->thr_c = thr; }
-    ws->above[tid] = n_px;                     // (the percentile histogram is black's: no bound)
-    s_above[tid] = n_px;
-  }
-  __syncthreads();
-  if (tid == 0) arena_reserve(ws, s_above[0], s_above[1]);
-}
-
 #ifndef SLG_STATS_MINB
 #define SLG_STATS_MINB 1     // stats_kernel workgroups per CU its registers are budgeted for
 #endif
-
-// The view's histogram copies summed into hg[0..511] by 256 lanes (lane t: bins t and t + 256),
-// every copy of both bins loaded before any is summed: one round trip (a loop over the two bins
-// took two, 1.6 us of a one-view call's stats launch).  pad: the zero padding past n_px, taken
-// off bins 0 and 256.  Agent-scope atomic loads: see stats_kernel's ticket.
-__device__ __attribute__((always_inline)) inline void sum_hist_copies(const uint32_t* hist_part, int tid, uint32_t pad,
-                                                                     uint32_t* hg) {
-  uint32_t v[2][kHistCopies];
-#pragma unroll
-  for (int r = 0; r < 2; ++r)
-#pragma unroll
-    for (int c = 0; c < kHistCopies; ++c)
-      v[r][c] = __hip_atomic_load(hist_part + c * 512 + tid + 256 * r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    uint32_t acc = 0;
-#pragma unroll
-    for (int c = 0; c < kHistCopies; ++c) acc += v[r][c];
-    hg[tid + 256 * r] = acc - (tid == 0 ? pad : 0u);
-  }
-}
 
 __global__ __launch_bounds__(kBlock, SLG_STATS_MINB) void stats_kernel(StatsParams p) {
   // 16 sub-histograms per kind (wave x lane&3), rows padded to 257 words so the copies of one
@@ -856,79 +292,6 @@ __global__ __launch_bounds__(kBlock) void hist_thresholds_kernel(const uint32_t*
   set_thresholds(hg, hist[512], n_px, thresh_mode == SLG_THRESH_OTSU, ws, reinterpret_cast<double*>(hg + 512), s_above);
 }
 
-// Otsu thresholds from the per-tile partial histograms a fused launch left in each view's
-// workspace slice (the carried "batch after next", hist_next_*): the lean counterpart of
-// stats_kernel for the streaming pipeline.  It runs on a side stream BESIDE a fused launch, so
-// it holds as few CU resources as it can: 2 KB of LDS, no frame reads, every partial of a
-// workgroup's tile range in flight at once (kPartsInFlight loads per lane), then <= 512 global
-// adds, a ticket, and the same Otsu tail as stats_kernel in the last arriver.
-constexpr int kPartsInFlight = 16;
-constexpr int kPartsLdsWords = 512 + 4 * kOtsuLds + 4;
-constexpr int kPartsBlocksMax = 64;         // workgroups per view (each sums a contiguous tile range)
-
-// One workgroup's share of "thresholds from partials" for one view: workgroup `block` of
-// `n_blocks` sums its contiguous range of the view's n_parts per-tile partials, adds them into
-// the view's histogram copies, takes a ticket; the last arriver runs Otsu, writes the mask
-// thresholds and resets the histogram state.  Also zeroes the view's look-back words (arming
-// the main launch that will use these thresholds; ordered by the kernel boundary).  256 lanes;
-// hg: kPartsLdsWords words of LDS (512 histogram words + 2 x kOtsuLds doubles + 2 int64,
-// 16-byte aligned), s_last: one.  Used by parts_kernel and by main3's finishing workgroups.
-__device__ __attribute__((always_inline)) inline void otsu_from_parts(const uint32_t* pp, WsHeader* ws, int64_t n_parts, int64_t n_px,
-                                int64_t n_state_words, int64_t pad_zero, int block, int n_blocks,
-                                uint32_t* hg, uint32_t* s_last) {
-  const int tid = threadIdx.x, wave = tid >> 6;
-  int64_t* s_above = reinterpret_cast<int64_t*>(hg + 512 + 4 * kOtsuLds);
-  const bool act = tid < kBlock;               // the work is laid out for 256 lanes (a 512-lane
-  uint32_t* hist_part = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ws) + kHistPartOff);
-  uint64_t* states = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(ws) + states_off(n_px));
-  if (act) {                                   // main3 workgroup's upper half only syncs)
-    for (int64_t i = int64_t(block) * kBlock + tid; i < n_state_words; i += int64_t(n_blocks) * kBlock)
-      states[i] = 0;
-    if (block == 0 && tid == 0) ws->lb_ticket = ws->lb_ticket_row = 0;
-
-    // thread t owns packed word t (bins 2t, 2t+1 of [white 0..255 | clip 256..511])
-    const int64_t per = (n_parts + n_blocks - 1) / n_blocks;
-    const int64_t t0 = int64_t(block) * per, t1 = t0 + per < n_parts ? t0 + per : n_parts;
-    uint32_t a0 = 0, a1 = 0;
-    for (int64_t k0 = t0; k0 < t1; k0 += kPartsInFlight) {
-      uint32_t v[kPartsInFlight];
-#pragma unroll
-      for (int j = 0; j < kPartsInFlight; ++j)
-        v[j] = k0 + j < t1 ? pp[(k0 + j) * kPartWords + tid] : 0u;
-#pragma unroll
-      for (int j = 0; j < kPartsInFlight; ++j) { a0 += v[j] & 0xffffu; a1 += v[j] >> 16; }
-    }
-    uint32_t* dst = hist_part + (block % kHistCopies) * 512 + 2 * tid;
-    if (a0) atomicAdd(dst, a0);
-    if (a1) atomicAdd(dst + 1, a1);
-  }
-
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (atomics only: see stats_kernel)
-  __syncthreads();
-  if (tid == 0) {
-    const uint32_t t = __hip_atomic_fetch_add(&ws->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *s_last = (t == uint32_t(n_blocks) - 1) ? 1u : 0u;
-  }
-  __syncthreads();
-  if (!*s_last) return;
-  if (act) sum_hist_copies(hist_part, tid, uint32_t(pad_zero), hg);
-  __syncthreads();
-  if (wave < 2) {                              // wave 0: white, wave 1: clip(w-b); concurrently
-    const double thr = otsu_wave(hg + 256 * wave, n_px, reinterpret_cast<double*>(hg + 512) + wave * kOtsuLds);
-    const int m = int_threshold(thr, wave == 0 ? 0 : -255);
-    const int64_t above = hist_at_least_wave(hg + 256 * wave, m, n_px);
-    if ((tid & 63) == 0) {
-      if (wave == 0) { ws->smin = m; ws->thr_s = thr; } else { ws->cmin = m; ws->thr_c = thr; }
-      ws->above[wave] = above;
-      s_above[wave] = above;
-    }
-  }
-  __syncthreads();
-  if (tid == 0) arena_reserve(ws, s_above[0], s_above[1]);
-  for (int i = tid; act && i < kHistCopies * 512; i += kBlock) hist_part[i] = 0;
-  if (tid == 0) { ws->max_diff_enc = 0; ws->ticket = 0; }
-}
-
 __global__ __launch_bounds__(kBlock) void parts_kernel(StatsParams p) {
   __shared__ __attribute__((aligned(16))) uint32_t hg[kPartsLdsWords];   // + the Otsu tail's LDS
   __shared__ uint32_t s_last;
@@ -937,6 +300,13 @@ __global__ __launch_bounds__(kBlock) void parts_kernel(StatsParams p) {
 }
 
 // ------------------------------------------------------------------ main kernel
+// Decode plan of one view: per axis, the frame index of the first pattern, the pairs to read,
+// the pre-shift and the post-shift (make_plan).
+struct Plan {
+  int32_t col_first, col_pairs, col_pre, col_post;
+  int32_t row_first, row_pairs, row_pre, row_post;
+};
+
 struct MainParams {
   // frames source
   const uint8_t* frames;
@@ -949,9 +319,7 @@ struct MainParams {
   const uint8_t* texture;
   int64_t n_px;
   int32_t width;
-  // decode plan (frame index of first pattern, pairs to read, pre-shift, post-shift)
-  int32_t col_first, col_pairs, col_pre, col_post;
-  int32_t row_first, row_pairs, row_pre, row_post;
+  Plan plan;
   // maps output
   int32_t* out_col;
   int32_t* out_row;
@@ -1144,8 +512,8 @@ __device__ inline void decode_lane(const MainParams& p, int64_t px0, bool tail, 
       if (valid != 0u) pre(w);                    // (white bytes: a gray capture's texture)
     }
     PlaneAcc qc = {{0, 0}, {0, 0}}, qr = {{0, 0}, {0, 0}};
-    const int np_c = PLAN ? ((PLAN >> 4) & 15) : p.col_pairs;
-    const int np_r = ROW_MODE == 0 ? 0 : (PLAN ? (PLAN & 15) : p.row_pairs);
+    const int np_c = PLAN ? ((PLAN >> 4) & 15) : p.plan.col_pairs;
+    const int np_r = ROW_MODE == 0 ? 0 : (PLAN ? (PLAN & 15) : p.plan.row_pairs);
     // compile-time trip count (kMaxBits pairs max), fully unrolled: only forward, wave-uniform
     // branches remain, so the loads of a batch stay in flight together (no vmcnt(0) per load)
     if (paired) {
@@ -1154,10 +522,10 @@ __device__ inline void decode_lane(const MainParams& p, int64_t px0, bool tail, 
         PairLd cl[kBatch], rl[kBatch];
 #pragma unroll
         for (int g = 0; g < kBatch; ++g)
-          if (b0 + g < np_c) cl[g] = ld_pair16(p, p.col_first + 2 * (b0 + g), vo);
+          if (b0 + g < np_c) cl[g] = ld_pair16(p, p.plan.col_first + 2 * (b0 + g), vo);
 #pragma unroll
         for (int g = 0; g < kBatch; ++g)
-          if (b0 + g < np_r) rl[g] = ld_pair16(p, p.row_first + 2 * (b0 + g), vo);
+          if (b0 + g < np_r) rl[g] = ld_pair16(p, p.plan.row_first + 2 * (b0 + g), vo);
 #pragma unroll
         for (int g = 0; g < kBatch; ++g)
           if (b0 + g < np_c) {
@@ -1182,14 +550,14 @@ __device__ inline void decode_lane(const MainParams& p, int64_t px0, bool tail, 
 #pragma unroll
       for (int g = 0; g < kBatch; ++g)
         if (b0 + g < np_c) {
-          cp[g] = ld_frame8(p, p.col_first + 2 * (b0 + g), lp);
-          ci[g] = ld_frame8(p, p.col_first + 2 * (b0 + g) + 1, lp);
+          cp[g] = ld_frame8(p, p.plan.col_first + 2 * (b0 + g), lp);
+          ci[g] = ld_frame8(p, p.plan.col_first + 2 * (b0 + g) + 1, lp);
         }
 #pragma unroll
       for (int g = 0; g < kBatch; ++g)
         if (b0 + g < np_r) {
-          rp[g] = ld_frame8(p, p.row_first + 2 * (b0 + g), lp);
-          ri[g] = ld_frame8(p, p.row_first + 2 * (b0 + g) + 1, lp);
+          rp[g] = ld_frame8(p, p.plan.row_first + 2 * (b0 + g), lp);
+          ri[g] = ld_frame8(p, p.plan.row_first + 2 * (b0 + g) + 1, lp);
         }
 #pragma unroll
       for (int g = 0; g < kBatch; ++g)
@@ -1206,8 +574,8 @@ __device__ inline void decode_lane(const MainParams& p, int64_t px0, bool tail, 
     }
     }
     uint32_t ac[4], ar[4];
-    acc_codes(qc, np_c, p.col_pre, p.col_post, ac);
-    acc_codes(qr, np_r, p.row_pre, p.row_post, ar);
+    acc_codes(qc, np_c, p.plan.col_pre, p.plan.col_post, ac);
+    acc_codes(qr, np_r, p.plan.row_pre, p.plan.row_post, ar);
 #pragma unroll
     for (int k = 0; k < kPx; ++k) {
       if constexpr (!MF) {
@@ -1438,13 +806,13 @@ __device__ inline bool decode_px(const MainParams& p, int64_t px, int& col, int&
     const uint8_t* f = p.frames + px;
     const int wv = f[0], bv = f[p.stride];
     uint32_t c = 0, r = 0;
-    for (int b = 0; b < p.col_pairs; ++b)
-      c = (c << 1) | uint32_t(f[int64_t(p.col_first + 2 * b) * p.stride] > f[int64_t(p.col_first + 2 * b + 1) * p.stride]);
-    col = int(gray2bin_x2(c << p.col_pre) << p.col_post);
+    for (int b = 0; b < p.plan.col_pairs; ++b)
+      c = (c << 1) | uint32_t(f[int64_t(p.plan.col_first + 2 * b) * p.stride] > f[int64_t(p.plan.col_first + 2 * b + 1) * p.stride]);
+    col = int(gray2bin_x2(c << p.plan.col_pre) << p.plan.col_post);
     if (ROW_MODE != 0) {
-      for (int b = 0; b < p.row_pairs; ++b)
-        r = (r << 1) | uint32_t(f[int64_t(p.row_first + 2 * b) * p.stride] > f[int64_t(p.row_first + 2 * b + 1) * p.stride]);
-      r = gray2bin_x2(r << p.row_pre) << p.row_post;
+      for (int b = 0; b < p.plan.row_pairs; ++b)
+        r = (r << 1) | uint32_t(f[int64_t(p.plan.row_first + 2 * b) * p.stride] > f[int64_t(p.plan.row_first + 2 * b + 1) * p.stride]);
+      r = gray2bin_x2(r << p.plan.row_pre) << p.plan.row_post;
     }
     row = int(r);
     return (wv >= p.ws->smin) & ((wv - bv) >= p.ws->cmin);
@@ -1697,8 +1065,7 @@ struct ViewIO {
   void* scratch_xyz;          // row_mode 2 row cloud
   uint8_t* scratch_bgr;
   int64_t stride;             // frame stride of this view
-  int32_t col_first, col_pairs, col_pre, col_post;   // decode plan of this view (frames present)
-  int32_t row_first, row_pairs, row_pre, row_post;
+  Plan plan;                  // decode plan of this view (frames present)
   const uint8_t* hn_white;    // batch after next: white / black of the view in this slot, whose
   const uint8_t* hn_black;    // Otsu histograms this launch computes per tile (NULL: none)
   uint32_t* hn_part;          // -> [n_tiles][kPartWords] of this view's workspace slice
@@ -1725,6 +1092,9 @@ struct Main3Params {
 };
 
 static_assert(sizeof(Main3Params) <= 4096, "kernel arguments");
+static_assert(sizeof(Plan) == 32 && offsetof(MainParams, plan) == 60 && offsetof(MainParams, out_col) == 96 &&
+              sizeof(MainParams) == 328 && offsetof(ViewIO, plan) == 104 && offsetof(ViewIO, hn_white) == 136 &&
+              sizeof(ViewIO) == 160, "kernel argument layout (Plan sits where its eight fields did)");
 
 __device__ inline MainParams view_params(const Main3Params& P, int view) {
   MainParams q = P.c;
@@ -1735,8 +1105,7 @@ __device__ inline MainParams view_params(const Main3Params& P, int view) {
   q.ws = io.ws; q.states = io.states;
   q.scratch_xyz = io.scratch_xyz; q.scratch_bgr = io.scratch_bgr;
   q.stride = io.stride;
-  q.col_first = io.col_first; q.col_pairs = io.col_pairs; q.col_pre = io.col_pre; q.col_post = io.col_post;
-  q.row_first = io.row_first; q.row_pairs = io.row_pairs; q.row_pre = io.row_pre; q.row_post = io.row_post;
+  q.plan = io.plan;
   return q;
 }
 
@@ -2256,47 +1625,6 @@ __global__ __launch_bounds__(kBlock) void row_tail_kernel(WsHeader* ws, const vo
   }
 }
 
-// Colour captures (the reference's phone path uploads canvas PNGs, frontend/App.tsx:234-247,
-// saved as-is by server/server.py:86): cv2.imread(f, 0) turns each frame to gray and
-// cv2.imread(files[0]) gives frame 0 as BGR.  One upload of the decoded RGB(A) frames feeds
-// both: gray planes into the frame stack and frame 0's BGR texture.  PNG: libpng's
-// png_do_rgb_to_gray for an 8-bit file without gamma tables (OpenCV's png_set_rgb_to_gray(png,
-// 1, 0.299, 0.587)): (9797 r + 19234 g + 3737 b) >> 15, truncated, r where r == g == b --
-// pinned to libpng 1.6.37 (tests/test_png_color.py); gAMA / sRGB / iCCP files never come here
-// (slg_png_zstream refuses them; the host decodes them).  BMP: OpenCV's BGR2GRAY 14-bit weights,
-// restated (parity unpinned: no OpenCV here).  16 pixels per lane: channel bytes are read as
-// 16 x C contiguous bytes.
-constexpr int kRgbPx = 16;
-__global__ __launch_bounds__(kBlock) void rgb_gray_kernel(const uint8_t* rgb, int32_t channels, int64_t n_px,
-                                                          int64_t src_stride, uint8_t* gray, int64_t gray_stride,
-                                                          uint8_t* bgr0, int32_t bmp) {
-  const int f = blockIdx.y;
-  const int64_t px0 = (int64_t(blockIdx.x) * kBlock + threadIdx.x) * kRgbPx;
-  if (px0 >= n_px) return;
-  const uint8_t* src = rgb + int64_t(f) * src_stride + px0 * channels;
-  uint8_t* dst = gray + int64_t(f) * gray_stride + px0;
-  const int n = n_px - px0 < kRgbPx ? int(n_px - px0) : kRgbPx;
-  uint32_t g4[kRgbPx / 4] = {0, 0, 0, 0};
-#pragma unroll
-  for (int k = 0; k < kRgbPx; ++k) {
-    if (k >= n) continue;
-    const uint32_t r = src[k * channels], g = src[k * channels + 1], b = src[k * channels + 2];
-    const uint32_t y = bmp ? (b * 1868u + g * 9617u + r * 4899u + 8192u) >> 14
-                           : (r == g && r == b) ? r : (r * 9797u + g * 19234u + b * 3737u) >> 15;
-    g4[k >> 2] |= (y & 0xffu) << (8 * (k & 3));
-    if (bgr0 && f == 0) {
-      bgr0[(px0 + k) * 3] = uint8_t(b);
-      bgr0[(px0 + k) * 3 + 1] = uint8_t(g);
-      bgr0[(px0 + k) * 3 + 2] = uint8_t(r);
-    }
-  }
-  if (n == kRgbPx && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-    *reinterpret_cast<uint4*>(dst) = make_uint4(g4[0], g4[1], g4[2], g4[3]);
-  } else {
-    for (int k = 0; k < n; ++k) dst[k] = uint8_t(g4[k >> 2] >> (8 * (k & 3)));
-  }
-}
-
 // slg_workspace_set_arena: the arena words of n slices' headers.
 __global__ __launch_bounds__(64) void set_arena_kernel(char* ws, int64_t stride, int n, unsigned long long* cursor,
                                                        int64_t cap, int mult) {
@@ -2307,15 +1635,6 @@ __global__ __launch_bounds__(64) void set_arena_kernel(char* ws, int64_t stride,
   h->arena_cap = cap;
   h->arena_mult = mult;
   h->arena_off = 0;
-}
-
-// Gray frame stack whose texture is frame 0 replicated (cv2.imread(f) of an 8-bit gray PNG):
-// bgr[i] = (g, g, g) with g = frame0[i].
-__global__ __launch_bounds__(kBlock) void gray_texture_kernel(const uint8_t* frame0, int64_t n_px, uint8_t* bgr) {
-  const int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x;
-  if (i >= n_px) return;
-  const uint8_t g = frame0[i];
-  bgr[3 * i] = g; bgr[3 * i + 1] = g; bgr[3 * i + 2] = g;
 }
 
 __global__ __launch_bounds__(kBlock) void pinhole_kernel(const double* rays, int64_t n_px, int width, double fx,
@@ -2338,21 +1657,8 @@ __global__ __launch_bounds__(kBlock) void pinhole_kernel(const double* rays, int
 }
 
 // ------------------------------------------------------------------ host side
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-int check_launch(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(SLG_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-  return SLG_OK;
-}
+thread_local char g_err[512] = "";         // slg_last_error(); written by slg_internal_fail alone
+const auto fail = slg_internal_fail;       // (this file's short name for it)
 
 int ceil_log2(int n) {
   int b = 0;
@@ -2360,18 +1666,25 @@ int ceil_log2(int n) {
   return b;
 }
 
-struct Plan {
-  int col_first, col_pairs, col_pre, col_post;
-  int row_first, row_pairs, row_pre, row_post;
-};
+int check_enough_frames(const slg_capture* cap) {
+  if (cap->n_frames < 4)
+    return fail(SLG_ERR_NOT_ENOUGH, "Not enough images (got %d, need at least 4).", cap->n_frames);
+  return SLG_OK;
+}
+
+// The slices of a launch lie ws_stride apart: checked once there is a second one.
+int check_ws_stride(bool several, int64_t ws_stride, int64_t n_px) {
+  if (several && (ws_stride < ws_total(n_px) || (ws_stride & 255)))
+    return fail(SLG_ERR_INVALID, "ws_stride too small or not 256-aligned");
+  return SLG_OK;
+}
 
 // Which frames each axis reads and how the code is shifted (processing.py:80-122,
 // sl_system.py:546-585).
 int make_plan(const slg_capture* cap, const slg_decode_params* dp, Plan* out) {   // out may be NULL
   Plan tmp;
   Plan* pl = out ? out : &tmp;
-  if (cap->n_frames < 4)
-    return fail(SLG_ERR_NOT_ENOUGH, "Not enough images (got %d, need at least 4).", cap->n_frames);
+  if (const int rc = check_enough_frames(cap)) return rc;
   if (dp->proj_cols < 1 || dp->proj_rows < 1) return fail(SLG_ERR_INVALID, "projector size must be positive");
   const int Bc = ceil_log2(dp->proj_cols), Br = ceil_log2(dp->proj_rows);
   if (Bc > kMaxBits || Br > kMaxBits)
@@ -2523,18 +1836,18 @@ int fill_calib(MainParams& mp, const slg_calib* c, const slg_tri_params* tp, int
   return SLG_OK;
 }
 
-int fill_out(MainParams& mp, const slg_cloud* out, const slg_tri_params* tp, int64_t n_px, void* ws) {
+// Output + workspace pointers of one view.
+int fill_view(ViewIO& io, const slg_cloud* out, const slg_tri_params* tp, int64_t n_px, void* ws) {
   if (!out || !out->xyz || !out->bgr || !out->count) return fail(SLG_ERR_INVALID, "output cloud buffers NULL");
   const int64_t need = tp->row_mode == 2 ? 2 * n_px : n_px;
   if (out->capacity < need) return fail(SLG_ERR_INVALID, "cloud capacity %lld < %lld", (long long)out->capacity, (long long)need);
-  mp.xyz = out->xyz;
-  mp.bgr = out->bgr;
-  mp.count = out->count;
-  mp.ws = reinterpret_cast<WsHeader*>(ws);
-  mp.states = reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + states_off(n_px));
-  mp.n_tiles = n_tiles_of(n_px);
-  mp.scratch_xyz = static_cast<char*>(ws) + scratch_xyz_off(n_px);
-  mp.scratch_bgr = reinterpret_cast<uint8_t*>(static_cast<char*>(ws) + scratch_bgr_off(n_px));
+  io.xyz = out->xyz;
+  io.bgr = out->bgr;
+  io.count = out->count;
+  io.ws = reinterpret_cast<WsHeader*>(ws);
+  io.states = reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + states_off(n_px));
+  io.scratch_xyz = static_cast<char*>(ws) + scratch_xyz_off(n_px);
+  io.scratch_bgr = reinterpret_cast<uint8_t*>(static_cast<char*>(ws) + scratch_bgr_off(n_px));
   return SLG_OK;
 }
 
@@ -2604,69 +1917,16 @@ std::string main3_symbol(const Main3Inst& k) {
          std::string(k.prof ? "Lb1E" : "Lb0E") + li(k.plan) + "EEvNS_11Main3ParamsE";
 }
 
-// Symbol names of this library's gfx950 code objects: the clang offload bundles in its own file
-// (found by dladdr), each gfx950 entry an ELF whose symbol tables are read.  File reads only --
-// no HIP call, so nothing here can trip the runtime's abort.  Empty when the file cannot be read.
+// Symbol names of this library's gfx950 code objects, read once from its own file (found by
+// dladdr; code_object.cpp).  File reads only -- no HIP call, so nothing here can trip the
+// runtime's abort.  Empty when the file cannot be read.
 const std::vector<std::string>& device_symbols() {
   static std::vector<std::string> names;
   static std::once_flag once;
   std::call_once(once, [] {
     Dl_info info{};
-    if (!dladdr(reinterpret_cast<void*>(&slg_version), &info) || !info.dli_fname) return;
-    FILE* f = fopen(info.dli_fname, "rb");
-    if (!f) return;
-    std::vector<uint8_t> b;
-    if (fseek(f, 0, SEEK_END) == 0) {
-      const long n = ftell(f);
-      if (n > 0 && fseek(f, 0, SEEK_SET) == 0) {
-        b.resize(size_t(n));
-        if (fread(b.data(), 1, b.size(), f) != b.size()) b.clear();
-      }
-    }
-    fclose(f);
-    auto u16 = [&](size_t o) { uint16_t v; memcpy(&v, &b[o], 2); return v; };
-    auto u32 = [&](size_t o) { uint32_t v; memcpy(&v, &b[o], 4); return v; };
-    auto u64 = [&](size_t o) { uint64_t v; memcpy(&v, &b[o], 8); return v; };
-    static const char kMagic[] = "__CLANG_OFFLOAD_BUNDLE__";
-    const size_t ml = sizeof(kMagic) - 1;
-    for (size_t at = 0; at + ml + 8 <= b.size(); ++at) {
-      if (b[at] != '_' || memcmp(&b[at], kMagic, ml) != 0) continue;
-      size_t e = at + ml;
-      const uint64_t n_ent = u64(e);
-      e += 8;
-      for (uint64_t k = 0; k < n_ent && e + 24 <= b.size(); ++k) {
-        const uint64_t off = u64(e), size = u64(e + 8), tl = u64(e + 16);
-        e += 24;
-        if (e + tl > b.size()) break;
-        const std::string triple(reinterpret_cast<const char*>(&b[e]), size_t(tl));
-        e += tl;
-        const size_t o = at + off;                 // the entry: an ELF64 code object
-        if (triple.find("gfx950") == std::string::npos || o + 64 > b.size() || off + size > b.size() - at ||
-            memcmp(&b[o], "\x7f" "ELF", 4) != 0)
-          continue;
-        const uint64_t shoff = u64(o + 0x28);
-        const uint16_t shentsize = u16(o + 0x3a), shnum = u16(o + 0x3c);
-        if (shentsize < 64 || o + shoff + uint64_t(shnum) * shentsize > b.size()) continue;
-        for (uint16_t si = 0; si < shnum; ++si) {
-          const size_t sh = o + shoff + size_t(si) * shentsize;
-          const uint32_t type = u32(sh + 4);
-          if (type != 2 && type != 11) continue;   // SHT_SYMTAB, SHT_DYNSYM
-          const uint64_t sym_off = u64(sh + 24), sym_size = u64(sh + 32), ent = u64(sh + 56);
-          const uint32_t link = u32(sh + 40);
-          if (ent < 24 || link >= shnum) continue;
-          const size_t strh = o + shoff + size_t(link) * shentsize;
-          const uint64_t str_off = u64(strh + 24), str_size = u64(strh + 32);
-          if (o + sym_off + sym_size > b.size() || o + str_off + str_size > b.size()) continue;
-          for (uint64_t q = 0; q + ent <= sym_size; q += ent) {
-            const uint32_t nm = u32(o + sym_off + q);
-            if (nm == 0 || nm >= str_size) continue;
-            const char* c = reinterpret_cast<const char*>(&b[o + str_off + nm]);
-            names.emplace_back(c, strnlen(c, size_t(str_size - nm)));
-          }
-        }
-      }
-    }
-    std::sort(names.begin(), names.end());
+    if (dladdr(reinterpret_cast<void*>(&slg_version), &info) && info.dli_fname)
+      names = slg_code_object_symbols(info.dli_fname);
   });
   return names;
 }
@@ -2706,16 +1966,6 @@ Main3Fn pick_main(int src, int row_mode, int x64, int rays, int plan, const char
   }
   g_last_main = hit;
   return hit->fn;
-}
-
-// Output + workspace pointers of one view (the per-view half of fill_out).
-int fill_view(ViewIO& io, const slg_cloud* out, const slg_tri_params* tp, int64_t n_px, void* ws) {
-  MainParams mp{};
-  const int rc = fill_out(mp, out, tp, n_px, ws);
-  if (rc) return rc;
-  io.xyz = mp.xyz; io.bgr = mp.bgr; io.count = mp.count; io.ws = mp.ws; io.states = mp.states;
-  io.scratch_xyz = mp.scratch_xyz; io.scratch_bgr = mp.scratch_bgr;
-  return SLG_OK;
 }
 
 // One main3 launch over mp.n_views views (<= kMaxViews), then the row_mode-2 tails.
@@ -2774,23 +2024,23 @@ int fused_batch(const slg_capture* caps, int n_views, const slg_decode_params* d
       return fail(SLG_ERR_UNSUPPORTED, "SLG_DBG phase records cannot run with a carried batch");
     for (int v = 0; v < n_next; ++v) {
       rc = check_capture(&next[v]);
+      if (!rc) rc = check_enough_frames(&next[v]);
       if (rc) return rc;
-      if (next[v].n_frames < 4)
-        return fail(SLG_ERR_NOT_ENOUGH, "Not enough images (got %d, need at least 4).", next[v].n_frames);
       if (next[v].height != caps[0].height || next[v].width != caps[0].width)
         return fail(SLG_ERR_INVALID, "next batch must share this batch's geometry");
     }
   }
+  std::vector<Plan> plans(static_cast<size_t>(n_views));   // one make_plan per view: it validates too
   for (int v = 0; v < n_views; ++v) {
-    rc = make_plan(&caps[v], dp, nullptr);
+    rc = make_plan(&caps[v], dp, &plans[size_t(v)]);
     if (rc) return rc;
   }
   const int64_t n_px = int64_t(caps[0].height) * caps[0].width;
   // every slice of this launch (its views, the carried next batch, the finished batch) is
   // ws_stride apart; the finished batch's slices are read with THIS batch's geometry and
   // decode parameters (include/slgpu.h, slg_decode_triangulate_batch_carry)
-  if ((n_views > 1 || n_next > 1 || n_fin > 1) && (ws_stride < ws_total(n_px) || (ws_stride & 255)))
-    return fail(SLG_ERR_INVALID, "ws_stride too small or not 256-aligned");
+  rc = check_ws_stride(n_views > 1 || n_next > 1 || n_fin > 1, ws_stride, n_px);
+  if (rc) return rc;
   Main3Params mp{};
   rc = fill_calib(mp.c, calib, tp, n_px, caps[0].width);
   if (rc) return rc;
@@ -2800,8 +2050,7 @@ int fused_batch(const slg_capture* caps, int n_views, const slg_decode_params* d
     int plan = -1;                                  // the views' common pair counts, else 0
     bool all_gray = true, any_gray = false;         // gray captures (texture NULL)
     for (int k = 0; k < mp.n_views; ++k) {
-      Plan pl;
-      make_plan(&caps[v0 + k], dp, &pl);
+      const Plan& pl = plans[size_t(v0 + k)];
       const int rp = tp->row_mode == 0 ? 0 : pl.row_pairs;     // row_mode 0 reads no row frame
       const int key = pl.col_pairs <= 15 && rp <= 15 ? (pl.col_pairs << 4) | rp : 0;
       plan = plan < 0 || plan == key ? key : 0;
@@ -2821,10 +2070,7 @@ int fused_batch(const slg_capture* caps, int n_views, const slg_decode_params* d
       io.frames = caps[v].frames;
       io.texture = caps[v].texture;
       io.stride = caps[v].frame_stride;
-      Plan pl;
-      make_plan(&caps[v], dp, &pl);
-      io.col_first = pl.col_first; io.col_pairs = pl.col_pairs; io.col_pre = pl.col_pre; io.col_post = pl.col_post;
-      io.row_first = pl.row_first; io.row_pairs = pl.row_pairs; io.row_pre = pl.row_pre; io.row_post = pl.row_post;
+      io.plan = plans[size_t(v)];
       if (v < n_next) {
         io.hn_white = next[v].frames;
         io.hn_black = next[v].frames + next[v].frame_stride;
@@ -2857,16 +2103,14 @@ int stats_batch(const slg_capture* caps, int n_views, const slg_decode_params* d
   if (!caps || n_views < 1 || !dp || !ws) return fail(SLG_ERR_INVALID, "NULL argument");
   if (dp->thresh_mode < 0 || dp->thresh_mode > 2) return fail(SLG_ERR_INVALID, "bad thresh_mode");
   for (int v = 0; v < n_views; ++v) {
-    const int rc = check_capture(&caps[v]);
+    int rc = check_capture(&caps[v]);
+    if (!rc) rc = check_enough_frames(&caps[v]);
     if (rc) return rc;
-    if (caps[v].n_frames < 4)
-      return fail(SLG_ERR_NOT_ENOUGH, "Not enough images (got %d, need at least 4).", caps[v].n_frames);
     if (caps[v].height != caps[0].height || caps[v].width != caps[0].width)
       return fail(SLG_ERR_INVALID, "all views of a batch must share one geometry");
   }
   const int64_t n_px = int64_t(caps[0].height) * caps[0].width;
-  if (n_views > 1 && (ws_stride < ws_total(n_px) || (ws_stride & 255)))
-    return fail(SLG_ERR_INVALID, "ws_stride too small or not 256-aligned");
+  if (const int rc = check_ws_stride(n_views > 1, ws_stride, n_px)) return rc;
   for (int v0 = 0; v0 < n_views; v0 += kMaxBatch) {
     const int nb = n_views - v0 < kMaxBatch ? n_views - v0 : kMaxBatch;
     const uint8_t* wh[kMaxBatch];
@@ -2881,226 +2125,9 @@ int stats_batch(const slg_capture* caps, int n_views, const slg_decode_params* d
   return SLG_OK;
 }
 
-// ------------------------------------------------------------------ ASCII PLY (host)
-// "%.4f" of a double exactly as Python formats it (correctly rounded, ties to even, sign of
-// negative zero kept, 'nan' / 'inf' / '-inf'): the value m*2^e times 10^4 is rounded with
-// 128-bit integer arithmetic and its digits are emitted directly (no printf: ~10x faster);
-// magnitudes >= 9.2e14 fall back to glibc's exact printf.  Writes at most kFmtMax chars at p.
-constexpr int kFmtMax = 400;
-char* fmt4(double x, char* p) {
-  if (isnan(x)) { memcpy(p, "nan", 3); return p + 3; }
-  if (isinf(x)) {
-    if (x < 0) { memcpy(p, "-inf", 4); return p + 4; }
-    memcpy(p, "inf", 3); return p + 3;
-  }
-  uint64_t bits;
-  memcpy(&bits, &x, 8);
-  const bool neg = bits >> 63;
-  const double ax = fabs(x);
-  if (ax >= 9.2e14) return p + snprintf(p, kFmtMax, "%.4f", x);
-  const int bexp = int((bits >> 52) & 0x7ff);
-  uint64_t m = bits & ((uint64_t(1) << 52) - 1);
-  int e;
-  if (bexp == 0) { e = -1074; } else { m |= uint64_t(1) << 52; e = bexp - 1075; }
-  unsigned __int128 v = (unsigned __int128)m * 10000u;
-  uint64_t n;                                   // round(|x| * 10^4), ties to even
-  if (e >= 0) {
-    n = uint64_t(v << e);
-  } else {
-    const int k = -e;
-    if (k >= 127) {
-      n = 0;
-    } else {
-      const unsigned __int128 q = v >> k;
-      const unsigned __int128 rem = v - (q << k);
-      const unsigned __int128 half = (unsigned __int128)1 << (k - 1);
-      n = uint64_t(q) + ((rem > half || (rem == half && (q & 1))) ? 1 : 0);
-    }
-  }
-  if (neg) *p++ = '-';
-  uint64_t ip = n / 10000u;
-  unsigned fr = unsigned(n % 10000u);
-  char tmp[24];
-  int t = 0;
-  do { tmp[t++] = char('0' + ip % 10); ip /= 10; } while (ip);
-  while (t) *p++ = tmp[--t];
-  p[0] = '.';
-  p[1] = char('0' + fr / 1000);
-  p[2] = char('0' + (fr / 100) % 10);
-  p[3] = char('0' + (fr / 10) % 10);
-  p[4] = char('0' + fr % 10);
-  return p + 5;
-}
-
-char* fmt_u8(unsigned v, char* p) {
-  if (v >= 100) *p++ = char('0' + v / 100);
-  if (v >= 10) *p++ = char('0' + (v / 10) % 10);
-  *p++ = char('0' + v % 10);
-  return p;
-}
-
-// ------------------------------------------------------------------ ASCII PLY on the device
-// The body of ProcessingLogic._save_ply (server/processing.py:245-248): one line per point,
-// f"{x:.4f} {y:.4f} {z:.4f} {r} {g} {b}\n", formatted by the GPU so the cloud never leaves HBM
-// as numbers and the host only writes bytes.  The same exact rounding as fmt4 (round(|x|*10^4)
-// on the exact binary value, ties to even, '-' from the sign bit); magnitudes >= 9.2e14 (the
-// host path prints those through glibc) raise the `bad` flag so the caller formats on the host.
-constexpr int kPlyBlock = 256;             // threads per workgroup
-constexpr int kPlyPts = 4;                 // consecutive points per thread
-constexpr int kPlyChunk = kPlyBlock * kPlyPts;
-constexpr int kPlyNumMax = 21;             // '-' + 15 integer digits + '.' + 4
-constexpr int kPlyLineMax = 3 * kPlyNumMax + 3 * 3 + 6;
-
-struct PlyWs {                              // device workspace header (include/slgpu.h)
-  int64_t total;                            // body bytes
-  int32_t bad;                              // a value the device cannot format exactly
-  int32_t pad;
-};
-
-// |x| * 10^4 rounded exactly; false when |x| >= 9.2e14, NaN or inf (handled by the caller)
-__device__ inline uint64_t fixed4(double x, bool& neg) {
-  const uint64_t bits = uint64_t(__double_as_longlong(x));
-  neg = bits >> 63;
-  const int bexp = int((bits >> 52) & 0x7ff);
-  uint64_t m = bits & ((uint64_t(1) << 52) - 1);
-  int e;
-  if (bexp == 0) { e = -1074; } else { m |= uint64_t(1) << 52; e = bexp - 1075; }
-  const unsigned __int128 v = (unsigned __int128)m * 10000u;   // < 2^67; e <= -3 below 9.2e14
-  const int k = -e;
-  if (k >= 127) return 0;
-  const unsigned __int128 q = v >> k;
-  const unsigned __int128 rem = v - (q << k);
-  const unsigned __int128 half = (unsigned __int128)1 << (k - 1);
-  return uint64_t(q) + ((rem > half || (rem == half && (uint64_t(q) & 1))) ? 1 : 0);
-}
-
-// the line of point i into o (kPlyLineMax bytes), its length; -1: not formattable here
-__device__ inline int ply_line(const double* xyz, const uint8_t* bgr, int64_t i, char* o) {
-  int len = 0;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const double x = xyz[3 * i + c];
-    if (!(fabs(x) < 9.2e14)) return -1;          // NaN, inf, or beyond the exact fast path
-    bool neg;
-    const uint64_t n = fixed4(x, neg);
-    if (neg) o[len++] = '-';
-    uint64_t ip = n / 10000u;
-    const unsigned fr = unsigned(n - ip * 10000u);
-    char tmp[16];
-    int t = 0;
-    do { tmp[t++] = char('0' + ip % 10u); ip /= 10u; } while (ip);
-    while (t) o[len++] = tmp[--t];
-    o[len++] = '.';
-    o[len++] = char('0' + fr / 1000u);
-    o[len++] = char('0' + (fr / 100u) % 10u);
-    o[len++] = char('0' + (fr / 10u) % 10u);
-    o[len++] = char('0' + fr % 10u);
-    o[len++] = ' ';
-  }
-#pragma unroll
-  for (int c = 2; c >= 0; --c) {                 // BGR -> "R G B"
-    const unsigned v = bgr[3 * i + c];
-    if (v >= 100) o[len++] = char('0' + v / 100);
-    if (v >= 10) o[len++] = char('0' + (v / 10) % 10);
-    o[len++] = char('0' + v % 10);
-    o[len++] = c ? ' ' : '\n';
-  }
-  return len;
-}
-
-__device__ inline int ply_thread_bytes(const double* xyz, const uint8_t* bgr, int64_t n, int64_t i0, int* bad) {
-  char line[kPlyLineMax];
-  int sum = 0;
-  for (int j = 0; j < kPlyPts; ++j) {
-    const int64_t i = i0 + j;
-    if (i >= n) break;
-    const int l = ply_line(xyz, bgr, i, line);
-    if (l < 0) { atomicOr(bad, 1); return 0; }
-    sum += l;
-  }
-  return sum;
-}
-
-// Block-wide exclusive scan of one int per thread (kPlyBlock threads): (prefix, total).
-__device__ inline int2 ply_block_scan(int x, int* s_w) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = x;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(incl, o);
-    if (lane >= o) incl += y;
-  }
-  if (lane == 63) s_w[wave] = incl;
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kPlyBlock / 64; ++w) {
-    off += w < wave ? s_w[w] : 0;
-    tot += s_w[w];
-  }
-  return make_int2(off + incl - x, tot);
-}
-
-// pass 1: bytes per chunk
-__global__ __launch_bounds__(kPlyBlock) void ply_len_kernel(const double* xyz, const uint8_t* bgr, int64_t n,
-                                                           int64_t* chunk, PlyWs* hdr) {
-  __shared__ int s_w[kPlyBlock / 64];
-  const int64_t i0 = int64_t(blockIdx.x) * kPlyChunk + int64_t(threadIdx.x) * kPlyPts;
-  const int b = ply_thread_bytes(xyz, bgr, n, i0, &hdr->bad);
-  const int2 sc = ply_block_scan(b, s_w);
-  if (threadIdx.x == 0) chunk[blockIdx.x] = sc.y;
-}
-
-// pass 2: exclusive offsets of the chunks (one workgroup, serial over 1024-chunk strides)
-__global__ __launch_bounds__(1024) void ply_scan_kernel(int64_t* chunk, int64_t n_chunks, PlyWs* hdr) {
-  __shared__ int64_t s_w[16];
-  __shared__ int64_t s_carry;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) s_carry = 0;
-  __syncthreads();
-  for (int64_t base = 0; base < n_chunks; base += 1024) {
-    const int64_t i = base + threadIdx.x;
-    const int64_t x = i < n_chunks ? chunk[i] : 0;
-    int64_t incl = x;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int64_t y = __shfl_up(incl, o);
-      if (lane >= o) incl += y;
-    }
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    int64_t off = s_carry;
-    for (int w = 0; w < wave; ++w) off += s_w[w];
-    if (i < n_chunks) chunk[i] = off + incl - x;
-    __syncthreads();
-    if (threadIdx.x == 1023) s_carry = off + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) hdr->total = s_carry;
-}
-
-// pass 3: every thread writes its points' lines at the chunk offset + its prefix
-__global__ __launch_bounds__(kPlyBlock) void ply_write_kernel(const double* xyz, const uint8_t* bgr, int64_t n,
-                                                             const int64_t* chunk, char* text, PlyWs* hdr) {
-  __shared__ int s_w[kPlyBlock / 64];
-  if (hdr->bad) return;                                      // the caller formats on the host
-  const int64_t i0 = int64_t(blockIdx.x) * kPlyChunk + int64_t(threadIdx.x) * kPlyPts;
-  const int b = ply_thread_bytes(xyz, bgr, n, i0, &hdr->bad);
-  const int2 sc = ply_block_scan(b, s_w);
-  char* o = text + chunk[blockIdx.x] + sc.x;
-  char line[kPlyLineMax];
-  for (int j = 0; j < kPlyPts; ++j) {
-    const int64_t i = i0 + j;
-    if (i >= n) break;
-    const int l = ply_line(xyz, bgr, i, line);
-    for (int k = 0; k < l; ++k) o[k] = line[k];
-    o += l;
-  }
-}
-
 }  // namespace
 
-// Error entry for the library's other translation units (csrc/gather.cpp).
+// The library's one error entry (internal.h).
 int slg_internal_fail(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
@@ -3164,8 +2191,7 @@ int32_t slg_decode_stats(const slg_capture* cap, const slg_decode_params* dp, vo
   int rc = check_capture(cap);
   if (rc) return rc;
   if (!dp || !workspace) return fail(SLG_ERR_INVALID, "NULL argument");
-  if (cap->n_frames < 4)
-    return fail(SLG_ERR_NOT_ENOUGH, "Not enough images (got %d, need at least 4).", cap->n_frames);
+  if ((rc = check_enough_frames(cap))) return rc;
   if (dp->thresh_mode < 0 || dp->thresh_mode > 2) return fail(SLG_ERR_INVALID, "bad thresh_mode");
   const int64_t n_px = int64_t(cap->height) * cap->width;
   return stats_launch(cap->frames, cap->frames + cap->frame_stride, n_px, dp, workspace,
@@ -3177,8 +2203,7 @@ int32_t slg_decode_histograms(const slg_capture* cap, const slg_decode_params* d
   int rc = check_capture(cap);
   if (rc) return rc;
   if (!dp || !workspace || !hist_out) return fail(SLG_ERR_INVALID, "NULL argument");
-  if (cap->n_frames < 4)
-    return fail(SLG_ERR_NOT_ENOUGH, "Not enough images (got %d, need at least 4).", cap->n_frames);
+  if ((rc = check_enough_frames(cap))) return rc;
   if (dp->thresh_mode != SLG_THRESH_OTSU && dp->thresh_mode != SLG_THRESH_PERCENTILE)
     return fail(SLG_ERR_INVALID, "histograms serve Otsu / percentile thresholds (manual ones need none)");
   if (reinterpret_cast<uintptr_t>(hist_out) & 3) return fail(SLG_ERR_INVALID, "hist_out must be 4-byte aligned");
@@ -3213,17 +2238,14 @@ int32_t slg_decode(const slg_capture* cap, const slg_decode_params* dp, void* wo
   if ((reinterpret_cast<uintptr_t>(col_out) | reinterpret_cast<uintptr_t>(row_out)) & 15 ||
       reinterpret_cast<uintptr_t>(mask_out) & 7)
     return fail(SLG_ERR_INVALID, "map outputs must be 16-byte (col,row) / 8-byte (mask) aligned");
-  Plan pl;
-  rc = make_plan(cap, dp, &pl);
+  MainParams mp{};
+  rc = make_plan(cap, dp, &mp.plan);
   if (rc) return rc;
   const int64_t n_px = int64_t(cap->height) * cap->width;
-  MainParams mp{};
   mp.frames = cap->frames;
   mp.stride = cap->frame_stride;
   mp.n_px = n_px;
   mp.width = cap->width;
-  mp.col_first = pl.col_first; mp.col_pairs = pl.col_pairs; mp.col_pre = pl.col_pre; mp.col_post = pl.col_post;
-  mp.row_first = pl.row_first; mp.row_pairs = pl.row_pairs; mp.row_pre = pl.row_pre; mp.row_post = pl.row_post;
   mp.out_col = col_out; mp.out_row = row_out; mp.out_mask = mask_out;
   mp.ws = reinterpret_cast<WsHeader*>(workspace);
   mp.n_tiles = n_tiles_of(n_px);
@@ -3241,19 +2263,15 @@ int32_t slg_triangulate(const slg_maps* maps, const slg_calib* calib, const slg_
       (reinterpret_cast<uintptr_t>(maps->mask) | reinterpret_cast<uintptr_t>(maps->texture)) & 7)
     return fail(SLG_ERR_INVALID, "maps must be 16-byte (col,row) / 8-byte (mask,texture) aligned");
   const int64_t n_px = int64_t(maps->height) * maps->width;
-  MainParams mp{};
-  int rc = fill_calib(mp, calib, tp, n_px, maps->width);
+  Main3Params m3{};
+  int rc = fill_calib(m3.c, calib, tp, n_px, maps->width);
   if (rc) return rc;
-  rc = fill_out(mp, out, tp, n_px, workspace);
+  rc = fill_view(m3.v[0], out, tp, n_px, workspace);
   if (rc) return rc;
-  mp.in_col = maps->col; mp.in_row = maps->row; mp.in_mask = maps->mask; mp.texture = maps->texture;
+  m3.c.n_tiles = n_tiles_of(n_px);
+  m3.n_views = 1;
   hipStream_t s = static_cast<hipStream_t>(stream);
   rc = stats_launch(nullptr, nullptr, n_px, nullptr, workspace, s);   // arms states only (manual mode)
-  if (rc) return rc;
-  Main3Params m3{};
-  m3.c = mp;
-  m3.n_views = 1;
-  rc = fill_view(m3.v[0], out, tp, n_px, workspace);
   if (rc) return rc;
   m3.v[0].in_col = maps->col; m3.v[0].in_row = maps->row; m3.v[0].in_mask = maps->mask;
   m3.v[0].texture = maps->texture;
@@ -3284,94 +2302,6 @@ int32_t slg_reconstruct(const slg_capture* cap, const slg_decode_params* dp, con
 int32_t slg_decode_triangulate(const slg_capture* cap, const slg_decode_params* dp, const slg_calib* calib,
                                const slg_tri_params* tp, void* workspace, const slg_cloud* out, void* stream) {
   return reconstruct_impl(cap, dp, calib, tp, workspace, out, stream, false);
-}
-
-int64_t slg_ply_format_bound(int64_t n) { return n < 0 ? -fail(SLG_ERR_INVALID, "n < 0") : n * kPlyLineMax; }
-
-int64_t slg_ply_format_ws_bytes(int64_t n) {
-  if (n < 0) return -fail(SLG_ERR_INVALID, "n < 0");
-  return int64_t(sizeof(PlyWs)) + 8 * ((n + kPlyChunk - 1) / kPlyChunk + 1);
-}
-
-int32_t slg_ply_format(const double* xyz, const uint8_t* bgr, int64_t n, char* text, void* ws, void* stream) {
-  if (n < 0 || !ws || (n > 0 && (!xyz || !bgr || !text))) return fail(SLG_ERR_INVALID, "bad argument");
-  const hipStream_t s = static_cast<hipStream_t>(stream);
-  PlyWs* hdr = static_cast<PlyWs*>(ws);
-  int64_t* chunk = reinterpret_cast<int64_t*>(hdr + 1);
-  if (hipMemsetAsync(hdr, 0, sizeof(PlyWs), s) != hipSuccess) return fail(SLG_ERR_HIP, "hipMemsetAsync");
-  if (n == 0) return SLG_OK;
-  const int64_t nc = (n + kPlyChunk - 1) / kPlyChunk;
-  if (nc > INT_MAX) return fail(SLG_ERR_UNSUPPORTED, "cloud too large");
-  hipLaunchKernelGGL(ply_len_kernel, dim3(unsigned(nc)), dim3(kPlyBlock), 0, s, xyz, bgr, n, chunk, hdr);
-  int rc = check_launch("ply_len_kernel");
-  if (rc) return rc;
-  hipLaunchKernelGGL(ply_scan_kernel, dim3(1), dim3(1024), 0, s, chunk, nc, hdr);
-  rc = check_launch("ply_scan_kernel");
-  if (rc) return rc;
-  hipLaunchKernelGGL(ply_write_kernel, dim3(unsigned(nc)), dim3(kPlyBlock), 0, s, xyz, bgr, n, chunk, text, hdr);
-  return check_launch("ply_write_kernel");
-}
-
-int64_t slg_ply_write(const char* path, const double* xyz, const uint8_t* bgr, int64_t n, int32_t n_threads) {
-  if (!path || n < 0 || (n > 0 && (!xyz || !bgr))) return -fail(SLG_ERR_INVALID, "bad argument");
-  // default: the CPUs this process may run on, at most 16 (the formatter is ~60 ns per point
-  // per thread; more threads only contend with the frame decoders of the batch pipeline)
-  int nt = n_threads > 0 ? n_threads : std::min(16, int(std::thread::hardware_concurrency()));
-  if (nt < 1) nt = 1;
-  if (int64_t(nt) * 4096 > n) nt = int(n / 4096) + 1;
-  std::vector<std::string> parts(static_cast<size_t>(nt));
-  auto work = [&](int t) {
-    const int64_t lo = n * t / nt, hi = n * (t + 1) / nt;
-    std::string& o = parts[size_t(t)];
-    o.reserve(size_t(hi - lo) * 40);
-    char line[3 * kFmtMax + 32];
-    for (int64_t i = lo; i < hi; ++i) {
-      char* p = line;
-      p = fmt4(xyz[3 * i], p); *p++ = ' ';
-      p = fmt4(xyz[3 * i + 1], p); *p++ = ' ';
-      p = fmt4(xyz[3 * i + 2], p); *p++ = ' ';
-      p = fmt_u8(bgr[3 * i + 2], p); *p++ = ' ';  // BGR -> "R G B" (processing.py:248)
-      p = fmt_u8(bgr[3 * i + 1], p); *p++ = ' ';
-      p = fmt_u8(bgr[3 * i], p); *p++ = '\n';
-      o.append(line, size_t(p - line));
-    }
-  };
-  std::vector<std::thread> th;
-  for (int t = 1; t < nt; ++t) th.emplace_back(work, t);
-  work(0);
-  for (auto& x : th) x.join();
-  char hdr[320];
-  const int hlen = snprintf(hdr, sizeof(hdr), "ply\nformat ascii 1.0\nelement vertex %lld\nproperty float x\n"
-                            "property float y\nproperty float z\nproperty uchar red\nproperty uchar green\n"
-                            "property uchar blue\nend_header\n", (long long)n);
-  // Each thread's part goes to its own offset with pwrite, in parallel (no serial copy through
-  // a stdio buffer: ~45 MB per C2 view).
-  std::vector<int64_t> off(size_t(nt) + 1);
-  off[0] = hlen;
-  for (int t = 0; t < nt; ++t) off[size_t(t) + 1] = off[size_t(t)] + int64_t(parts[size_t(t)].size());
-  const int fd = open(path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
-  if (fd < 0) return -fail(SLG_ERR_INVALID, "cannot open %s", path);
-  auto put = [fd](const char* b, int64_t len, int64_t at) {
-    while (len > 0) {
-      const ssize_t w = pwrite(fd, b, size_t(len), off_t(at));
-      if (w < 0 && errno == EINTR) continue;
-      if (w <= 0) return false;
-      b += w; len -= w; at += w;
-    }
-    return true;
-  };
-  std::vector<char> ok(size_t(nt) + 1, 1);
-  ok[size_t(nt)] = put(hdr, hlen, 0);
-  th.clear();
-  for (int t = 1; t < nt; ++t)
-    th.emplace_back([&, t] { ok[size_t(t)] = put(parts[size_t(t)].data(), int64_t(parts[size_t(t)].size()), off[size_t(t)]); });
-  ok[0] = put(parts[0].data(), int64_t(parts[0].size()), off[0]);
-  for (auto& x : th) x.join();
-  const bool closed = close(fd) == 0;
-  for (char c : ok)
-    if (!c) return -fail(SLG_ERR_INVALID, "write failed: %s", path);
-  if (!closed) return -fail(SLG_ERR_INVALID, "write failed: %s", path);
-  return off[size_t(nt)];
 }
 
 int32_t slg_reconstruct_batch(const slg_capture* caps, int32_t n_views, const slg_decode_params* dp,
@@ -3431,8 +2361,7 @@ int32_t slg_decode_stats_partials_batch(int32_t n_views, int32_t height, int32_t
   if (n_views < 1 || !dp || !workspace || height < 1 || width < 1) return fail(SLG_ERR_INVALID, "bad argument");
   if (dp->thresh_mode != SLG_THRESH_OTSU) return fail(SLG_ERR_UNSUPPORTED, "partial histograms are Otsu only");
   const int64_t n_px = int64_t(height) * width;
-  if (n_views > 1 && (ws_stride < ws_total(n_px) || (ws_stride & 255)))
-    return fail(SLG_ERR_INVALID, "ws_stride too small or not 256-aligned");
+  if (const int rc = check_ws_stride(n_views > 1, ws_stride, n_px)) return rc;
   char* ws = static_cast<char*>(workspace);
   for (int v0 = 0; v0 < n_views; v0 += kMaxBatch) {
     const int nb = n_views - v0 < kMaxBatch ? n_views - v0 : kMaxBatch;
@@ -3441,20 +2370,6 @@ int32_t slg_decode_stats_partials_batch(int32_t n_views, int32_t height, int32_t
     if (rc) return rc;
   }
   return SLG_OK;
-}
-
-int32_t slg_rgb_to_gray(const uint8_t* rgb, int32_t channels, int64_t n_pixels, int64_t src_stride, int32_t n_frames,
-                        uint8_t* gray, int64_t gray_stride, uint8_t* bgr0, int32_t weights, void* stream) {
-  if (!rgb || !gray || n_pixels < 1 || n_frames < 1 || (channels != 3 && channels != 4))
-    return fail(SLG_ERR_INVALID, "bad rgb_to_gray argument");
-  if (src_stride < n_pixels * channels || gray_stride < n_pixels)
-    return fail(SLG_ERR_INVALID, "strides smaller than a frame");
-  if (weights != SLG_GRAY_PNG && weights != SLG_GRAY_BMP) return fail(SLG_ERR_INVALID, "bad weights");
-  const int64_t per_block = int64_t(kBlock) * kRgbPx;
-  hipLaunchKernelGGL(rgb_gray_kernel, dim3(unsigned((n_pixels + per_block - 1) / per_block), unsigned(n_frames)),
-                     dim3(kBlock), 0, static_cast<hipStream_t>(stream), rgb, channels, n_pixels, src_stride, gray,
-                     gray_stride, bgr0, weights == SLG_GRAY_BMP ? 1 : 0);
-  return check_launch("rgb_gray_kernel");
 }
 
 int32_t slg_workspace_set_arena(void* workspace, int64_t ws_stride, int32_t n_slices, int64_t* cursor,
@@ -3469,13 +2384,6 @@ int32_t slg_workspace_set_arena(void* workspace, int64_t ws_stride, int32_t n_sl
                      reinterpret_cast<unsigned long long*>(cursor), cursor ? capacity_points : 0,
                      cursor ? points_per_valid : 0);
   return check_launch("set_arena_kernel");
-}
-
-int32_t slg_gray_texture(const uint8_t* frame0, int64_t n_pixels, uint8_t* bgr, void* stream) {
-  if (!frame0 || !bgr || n_pixels < 1) return fail(SLG_ERR_INVALID, "bad gray_texture argument");
-  hipLaunchKernelGGL(gray_texture_kernel, dim3(unsigned((n_pixels + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                     static_cast<hipStream_t>(stream), frame0, n_pixels, bgr);
-  return check_launch("gray_texture_kernel");
 }
 
 int32_t slg_rays_match_pinhole(const double* rays, int32_t height, int32_t width, double fx, double fy, double cx,

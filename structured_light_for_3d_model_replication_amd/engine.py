@@ -385,7 +385,7 @@ class Reconstructor:
 
 
 MAX_VIEWS_PER_LAUNCH = 16     # kMaxViews in csrc/slgpu.hip
-WS_ABOVE_OFF = 3136           # offsetof(WsHeader, above) in csrc/slgpu.hip (static_assert there)
+WS_ABOVE_OFF = 3136           # offsetof(WsHeader, above) in csrc/workspace.h (static_assert there)
 WS_TOTALS_OFF = 3120          # offsetof(WsHeader, totals)
 
 

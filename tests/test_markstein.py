@@ -1,4 +1,4 @@
-"""The kernels' Markstein division (csrc/slgpu.hip div_rn) equals IEEE division: compiled and
+"""The kernels' Markstein division (csrc/otsu.h div_rn) equals IEEE division: compiled and
 run on the host over random operands from the ranges the kernels use (tools/markstein_check.c).
 The GPU side is covered by the bit-exact float64 XYZ parity tests (tests/test_gpu_parity.py)."""
 import os

@@ -81,7 +81,7 @@ def test_otsu_matches_exact_rational(seed):
 
 
 def percentile_from_hist(h, n):
-    """Float32 restatement used by the GPU stats kernel (slgpu.hip:percentile95_from_hist)."""
+    """Float32 restatement used by the GPU stats kernel (csrc/otsu.h percentile95_from_hist)."""
     cum = np.cumsum(h)
 
     def kth(k):

@@ -1,4 +1,4 @@
-"""The Otsu tail's speculative quotient (csrc/slgpu.hip: mu1_run<true>), restated with exactly
+"""The Otsu tail's speculative quotient (csrc/otsu.h otsu_wave, step 3), restated with exactly
 rounded fp64 arithmetic: m = fma(a, y, a * (fma(-q, y, 1) * y)) with y = RN(1/q) must be a
 faithful a / q, RN(a / q) in practice, and the kernel's check RN(m + fma(-q, m, a) * y) must
 always land on RN(a / q) (Markstein), so a miss is always caught and rerun exactly.  The chain

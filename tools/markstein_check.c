@@ -1,4 +1,4 @@
-/* markstein_check.c -- CPU check of the division used by the kernels (csrc/slgpu.hip div_rn):
+/* markstein_check.c -- CPU check of the division used by the kernels (csrc/otsu.h div_rn):
  * q = RN(a/b) from y = RN(1/b) with two FMA corrections, against IEEE a/b, on random operands
  * from the ranges the kernels feed it (Otsu: a in [0, 255], b in (eps, 1]; rays: a = u - cx
  * over pixel coordinates, b = fx, and a = x or y over a norm b >= 1).

@@ -1,4 +1,4 @@
-// otsu_probe.hip -- times the Otsu tail (otsu_wave of csrc/slgpu.hip, OpenCV's sequential fp64
+// otsu_probe.hip -- times the Otsu tail (otsu_wave of csrc/otsu.h, OpenCV's sequential fp64
 // chains) on one wave, alone on the GPU, with s_memrealtime (100 MHz) around each part, and
 // checks its threshold against the host restatement below (the same loop as the oracle's
 // otsu_from_hist, oracle/sl_oracle.py).  Histograms: argv[1] = a file of uint32 [k][256] (e.g.
@@ -7,8 +7,11 @@
 //   hipcc -O3 --offload-arch=gfx950 -std=c++17 -ffp-contract=off tools/otsu_probe.hip -o /tmp/otsu_probe
 __device__ unsigned long long g_otsu_marks[8];
 #define SLG_OTSU_MARK(k) (__builtin_amdgcn_s_waitcnt(0), g_otsu_marks[k] = __builtin_amdgcn_s_memtime())
-#include "../structured_light_for_3d_model_replication_amd/csrc/slgpu.hip"
+#include "../structured_light_for_3d_model_replication_amd/csrc/workspace.h"
+#include "../structured_light_for_3d_model_replication_amd/csrc/otsu.h"
 
+#include <math.h>
+#include <stdio.h>
 
 #include <float.h>
 #include <algorithm>
