@@ -409,9 +409,10 @@ int32_t slg_gather_destroy(slg_gather_comm *comm);
 int32_t slg_gatherv_plan(int32_t n_ranks, int32_t rank, int32_t root, int64_t send_bytes,
                          const int64_t *recv_bytes, int64_t *offsets, int32_t *recv_from);
 
-/* ---- Point-cloud cleanup on the device (csrc/cloud_filter.hip): the two deterministic
- * neighbour filters of the reference's cleanup tab, on a packed DEVICE cloud (xyz float64 [n][3]),
- * so a reconstructed view is cleaned without leaving HBM.
+/* ---- Point-cloud cleanup on the device (csrc/cloud_filter.hip): the three deterministic
+ * neighbour steps of the reference's cleanup tab (two filters, and DBSCAN with the largest-cluster
+ * pick: slg_dbscan, below), on a packed DEVICE cloud (xyz float64 [n][3]), so a reconstructed view
+ * is cleaned without leaving HBM.
  *   slg_radius_outlier      <- ProcessingLogic.remove_radius_outlier (server/processing.py:430-448)
  *   slg_statistical_outlier <- ProcessingLogic.remove_outliers (server/processing.py:367-388,620)
  *   slg_cloud_select        <- the select_by_index that follows either (ascending indices)
@@ -436,7 +437,25 @@ int32_t slg_gatherv_plan(int32_t n_ranks, int32_t rank, int32_t root, int64_t se
  * (isolated points) for the whole-cloud kernel.
  * slg_cloud_select packs the points with keep != 0, in input order, into out (xyz float64, bgr;
  * bgr / out->bgr may be NULL; *out->count = points written, at most out->capacity) and their
- * input indices into index_out (int64 [n] or NULL).  It uses ws but leaves the status word. */
+ * input indices into index_out (int64 [n] or NULL).  It uses ws but leaves the status word.
+ *
+ *   slg_dbscan              <- PointCloud.cluster_dbscan + the largest-label pick of
+ *                              ProcessingLogic.keep_largest_cluster (server/processing.py:391-427)
+ * Semantics (Open3D's ClusterDBSCAN as published, restated in closed form; the labels are a pure
+ * function of the input): with the radius filter's counts at radius = eps,
+ *   core[i] = counts[i] >= min_points;  two core points are linked when d2 < eps*eps;  a cluster's
+ *   core set is a connected component of that graph;  components are numbered 0..n_clusters-1 in
+ *   ascending order of their smallest input index;  a non-core point takes the lowest label among
+ *   its core neighbours, or -1 (noise) when it has none.
+ *   Largest cluster: the label with the most members (core and border), the lowest label among
+ *   equals, -1 when there is no cluster;  largest_keep[i] = labels[i] == that label (all 0 when
+ *   there is none).
+ * ws is slg_filter_ws_bytes(n, 0) bytes; labels_out is int32 [n] in input order;
+ * largest_keep_out (uint8 [n]) and info_out (int32 [4] = n_clusters, largest_label,
+ * largest_count, n_noise) may be NULL.  Asynchronous on `stream`, no host synchronisation; the
+ * status word at the front of ws as for slg_radius_outlier (radius = eps).  SLG_ERR_INVALID for
+ * n <= 0, eps <= 0 or NaN, min_points < 0, or a NULL xyz, labels_out or ws; SLG_ERR_UNSUPPORTED
+ * above 2^30 points. */
 #define SLG_FILTER_BAD_NONFINITE 1
 #define SLG_FILTER_BAD_EXTENT 2
 int64_t slg_filter_ws_bytes(int64_t n, int32_t k);
@@ -447,6 +466,12 @@ int32_t slg_statistical_outlier(const double *xyz, int64_t n, int32_t nb_neighbo
                                 double *stats_out, void *stream);
 int32_t slg_cloud_select(const double *xyz, const uint8_t *bgr, int64_t n, const uint8_t *keep,
                          const slg_cloud *out, int64_t *index_out, void *ws, void *stream);
+int32_t slg_dbscan(const double *xyz, int64_t n, double eps, int32_t min_points,
+                   void *ws, int64_t ws_bytes,
+                   int32_t *labels_out,          /* [n]: -1 noise, else 0..n_clusters-1 */
+                   uint8_t *largest_keep_out,    /* [n] or NULL */
+                   int32_t *info_out,            /* [4] or NULL: n_clusters, largest_label, largest_count, n_noise */
+                   void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,11 +1,12 @@
 """Point clouds on the device and their cleanup filters (``csrc/cloud_filter.hip``).
 
-``PointCloud`` is a packed float64 ``xyz`` + uint8 BGR ``bgr`` pair in HBM; :func:`radius_outlier`
-and :func:`statistical_outlier` are the two deterministic neighbour filters of the reference's
-cleanup tab (``ProcessingLogic.remove_radius_outlier``, ``server/processing.py:430-448``, and
-``ProcessingLogic.remove_outliers``, ``server/processing.py:367-388``), run on that cloud without
-the PLY round trip through the host.  Semantics: ``include/slgpu.h`` and DESIGN.md §9 (Open3D's
-published rules restated; parity with an installed Open3D is unpinned).
+``PointCloud`` is a packed float64 ``xyz`` + uint8 BGR ``bgr`` pair in HBM; :func:`radius_outlier`,
+:func:`statistical_outlier` and :func:`largest_cluster` are the three deterministic neighbour
+steps of the reference's cleanup tab (``ProcessingLogic.remove_radius_outlier``,
+``server/processing.py:430-448``, ``ProcessingLogic.remove_outliers``, ``:367-388``, and
+``ProcessingLogic.keep_largest_cluster``, ``:391-427``), run on that cloud without the PLY round
+trip through the host.  Semantics: ``include/slgpu.h`` and DESIGN.md §9 (Open3D's published rules
+restated; parity with an installed Open3D is unpinned).
 
 The PLY reader takes exactly the file ``ProcessingLogic._save_ply`` writes (``ply.header``): ASCII,
 ``x y z red green blue``.  Anything else raises ``ValueError`` saying what differs.
@@ -196,6 +197,25 @@ def statistical_mask(xyz: torch.Tensor, nb_neighbors: int, std_ratio: float, str
     return keep, avg, stats
 
 
+def dbscan_labels(xyz: torch.Tensor, eps: float, min_points: int, stream=None):
+    """``(labels int32 [n], keep uint8 [n], info int32 [4])`` on the device: Open3D's
+    ``cluster_dbscan`` labels in closed form (``-1`` noise, else ``0..n_clusters-1`` in ascending
+    order of each cluster's smallest core index), ``keep = labels == largest label``, and
+    ``info = (n_clusters, largest_label, largest_count, n_noise)``."""
+    xyz = _check_xyz(xyz)
+    n = xyz.shape[0]
+    with torch.cuda.device(xyz.device):
+        ws = _workspace(n, 0, xyz.device)
+        labels = torch.empty(n, dtype=torch.int32, device=xyz.device)
+        keep = torch.empty(n, dtype=torch.uint8, device=xyz.device)
+        info = torch.empty(4, dtype=torch.int32, device=xyz.device)
+        rc = N.lib().slg_dbscan(E._vp(xyz), n, float(eps), int(min_points), E._vp(ws), ws.numel(), E._vp(labels),
+                                E._vp(keep), E._vp(info), E._stream(stream))
+        _raise(rc)
+        _check_status(ws, "dbscan")
+    return labels, keep, info
+
+
 def _raise(rc: int) -> None:
     if rc == N.SLG_ERR_INVALID:
         raise ValueError(N.lib().slg_last_error().decode(errors="replace"))
@@ -235,5 +255,20 @@ def statistical_outlier(pc, nb_neighbors: int, std_ratio: float, return_index: b
     if not pc.has_points():
         raise ValueError("Point cloud is empty.")
     keep, _, _ = statistical_mask(pc.xyz, nb_neighbors, std_ratio)
+    out, idx = select(pc, keep)
+    return (out, idx) if return_index else out
+
+
+def largest_cluster(pc, eps: float, min_points: int, return_index: bool = False):
+    """Open3D ``cluster_dbscan`` + the largest-label pick of ``keep_largest_cluster`` +
+    ``select_by_index`` on the device: a new ``PointCloud`` of the largest cluster's points in
+    input order (the lowest label among equally large ones).  When every point is noise the input
+    cloud itself comes back, with indices ``arange(n)``."""
+    pc = as_point_cloud(pc)
+    if not pc.has_points():
+        raise ValueError("Point cloud is empty.")
+    _, keep, info = dbscan_labels(pc.xyz, eps, min_points)
+    if int(info[0].item()) == 0:
+        return (pc, torch.arange(len(pc), dtype=torch.int64, device=pc.xyz.device)) if return_index else pc
     out, idx = select(pc, keep)
     return (out, idx) if return_index else out

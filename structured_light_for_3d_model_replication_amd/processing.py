@@ -403,6 +403,25 @@ class ProcessingLogic:
             print(f"[Radius Outlier] Saved to {output_path}")
         return inlier_cloud if return_obj else None
 
+    @staticmethod
+    def keep_largest_cluster(input_data, output_path=None, eps=5.0, min_points=200, return_obj=False):
+        """DBSCAN on the device, then only the largest cluster (``server/processing.py:391-427``);
+        the same two differences from the reference as :meth:`remove_outliers`.  When every point
+        is noise the input cloud comes back before any save, as in the reference."""
+        from . import cloud as CL
+        print(f"[Cluster] Processing...")
+        pcd = ProcessingLogic._load_pcd(input_data)
+        if not pcd.has_points():
+            raise ValueError("Point cloud is empty.")
+        cleaned_pcd = CL.largest_cluster(pcd, eps, min_points)
+        if cleaned_pcd is pcd:               # no cluster at all
+            return pcd if return_obj else None
+        print(f"[Cluster] Kept largest group: {len(cleaned_pcd)} pts")
+        if output_path:
+            ProcessingLogic._save_ply(*cleaned_pcd.numpy(), output_path)
+            print(f"[Cluster] Saved to {output_path}")
+        return cleaned_pcd if return_obj else None
+
 
 def batch_views() -> int:
     """Views per batched launch in batch mode: ``SLG_BATCH_VIEWS`` (1..16), default 1.  The file

@@ -1,0 +1,254 @@
+"""Device DBSCAN (slg_dbscan, cloud.dbscan_labels / largest_cluster, keep_largest_cluster) against
+the closed-form restatement (cluster_ref.closed_labels): labels, the largest-cluster mask, the
+info words and the selected cloud's bits, colours and indices, all exactly."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import cloud_ref as R
+import cluster_cases as K
+import cluster_ref as CR
+from test_gpu_cloud_filter import NB, RADIUS, RATIO, bits, dev, oracle_cloud
+from test_gpu_cloud_filter import K as KNN
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def base():
+    """{row_mode: (P, C)} of the smoke view, computed once and left unchanged."""
+    out = {}
+    for rm in (1, 2):
+        (P, C), _ = oracle_cloud((192, 128), 25.0, 1, rm)
+        P.setflags(write=False)
+        C.setflags(write=False)
+        out[rm] = (P, C)
+    return out
+
+
+@pytest.fixture(scope="module")
+def CL():
+    from structured_light_for_3d_model_replication_amd import cloud
+    return cloud
+
+
+def colours(n):
+    return (np.arange(3 * n, dtype=np.int64).reshape(n, 3) % 251).astype(np.uint8)
+
+
+def check(CL, P, C, eps, min_points, graph=None):
+    """Runs the device on (P, C) and compares everything with the restatement; returns the
+    reference labels and the graph."""
+    graph = graph or CR.neighbour_graph(P, eps)
+    ref = CR.closed_labels(graph, min_points)
+    info_ref = CR.info(ref)
+    keep_ref = (ref == info_ref[1]) & (info_ref[0] > 0)
+    pc = CL.PointCloud(P, C)
+    labels, keep, info = CL.dbscan_labels(pc.xyz, eps, min_points)
+    labels, keep, info = labels.cpu().numpy(), keep.cpu().numpy(), info.cpu().numpy()
+    print("info device", info.tolist(), "reference", info_ref)
+    assert labels.dtype == np.int32 and np.array_equal(labels, ref)
+    assert info.tolist() == info_ref
+    assert np.array_equal(keep.astype(bool), keep_ref)
+    out, idx = CL.largest_cluster(pc, eps, min_points, return_index=True)
+    if info_ref[0] == 0:
+        assert out is pc and np.array_equal(idx.cpu().numpy(), np.arange(len(P)))
+    else:
+        Po, Co = out.numpy()
+        assert len(out) == info_ref[2]
+        assert np.array_equal(idx.cpu().numpy(), np.flatnonzero(keep_ref))
+        assert np.array_equal(bits(Po), bits(P[keep_ref])) and np.array_equal(Co, C[keep_ref])
+    return ref, graph
+
+
+@pytest.mark.parametrize("case", sorted(K.BASE))
+def test_base_table(CL, base, case):
+    rm, eps, mp = case
+    points, clusters, big, noise, contested = K.BASE[case]
+    P, C = base[rm]
+    g = CR.neighbour_graph(P, eps)
+    ref = CR.closed_labels(g, mp)
+    n_clusters, label, count, n_noise = CR.info(ref)                # preconditions on the inputs
+    assert (len(P), n_clusters, n_noise) == (points, clusters, noise)
+    if big is not None:
+        assert count == big[1] and big[0] in (None, label)
+    assert CR.contested(g, mp, ref) == contested
+    check(CL, P, C, eps, mp, graph=g)
+
+
+@pytest.mark.parametrize("first", [True, False])
+def test_bridge(CL, first):
+    P, b = K.bridge(first)
+    g = CR.neighbour_graph(P, K.BRIDGE_EPS)
+    assert not CR.core_mask(g, K.BRIDGE_MIN)[b]
+    ref, _ = check(CL, P, colours(len(P)), K.BRIDGE_EPS, K.BRIDGE_MIN, graph=g)
+    assert CR.contested(g, K.BRIDGE_MIN, ref) == 1
+    hi = 1 if first else 0
+    assert ref[b] == 0 and ref[hi] == 0 and ref[hi + 13] == 1 and P[hi, 0] > P[hi + 13, 0]
+
+
+def test_strictness(CL):
+    P = K.lattice5()
+    C = colours(len(P))
+    ref, _ = check(CL, P, C, 5.0, 1)
+    assert np.array_equal(ref, np.arange(len(P))) and CR.largest(ref) == (0, 1)
+    ref, _ = check(CL, P, C, 5.0, 2)
+    assert np.all(ref == -1)
+    ref, _ = check(CL, P, C, 5.000001, 2)
+    assert np.all(ref == 0)
+
+
+def test_decimal_lattice(CL):
+    P = K.decimal_lattice()
+    g = CR.brute_graph(P, 0.3)
+    assert not np.array_equal(np.diff(g[0]), R.brute_radius_counts(P, 0.3 * (1 - 1e-9)))   # rounding decides some
+    for mp in (10, 60):
+        assert (mp == 10) == bool(CR.core_mask(g, mp).all()) and CR.core_mask(g, mp).any()
+        check(CL, P, colours(len(P)), 0.3, mp, graph=g)
+
+
+def test_long_chain(CL):
+    P = K.helix()
+    assert len(P) == 20000
+    ref, g = check(CL, P, colours(len(P)), K.HELIX_EPS, K.HELIX_MIN)
+    assert np.all(ref == 0) and np.count_nonzero(~CR.core_mask(g, K.HELIX_MIN)) == 2
+    P = K.helix(drop=7000)
+    ref, _ = check(CL, P, colours(len(P)), K.HELIX_EPS, K.HELIX_MIN)
+    assert sorted(np.bincount(ref).tolist()) == [7000, 12999] and ref[0] == 0
+
+
+def test_tie(CL):
+    P = K.tie()
+    ref, _ = check(CL, P, colours(len(P)), 1.0, 5)
+    assert ref.tolist() == [0] * 20 + [1] * 20
+
+
+def test_crowded_cell(CL, base):
+    """5,000 points inside one cell's volume on top of the base cloud: tiles and query batches
+    past the first, and thousands of lanes uniting into one set."""
+    P0, _ = base[1]
+    rng = np.random.default_rng(11)
+    P = np.vstack([P0, P0[len(P0) // 2] + rng.uniform(-2.0, 2.0, (5000, 3))])
+    g = CR.neighbour_graph(P, RADIUS)
+    assert np.diff(g[0]).max() > 5000
+    ref, _ = check(CL, P, colours(len(P)), RADIUS, 3000, graph=g)
+    assert CR.info(ref)[:3] == [1, 0, 5063]
+
+
+def test_duplicates(CL, base):
+    P0, _ = base[1]
+    P = np.vstack([P0[:3000], np.repeat(P0[1500][None] + 0.5, 25, 0)])
+    ref, _ = check(CL, P, colours(len(P)), 2.0, 25)
+    assert np.all(ref[-25:] >= 0)
+
+
+def test_small_n(CL, base):
+    P0, _ = base[1]
+    ref, _ = check(CL, P0[:1], colours(1), 5.0, 1)
+    assert ref.tolist() == [0]
+    ref, _ = check(CL, P0[:1], colours(1), 5.0, 2)
+    assert ref.tolist() == [-1]
+    ref, _ = check(CL, P0[:50], colours(50), RADIUS, 51)               # min_points > n
+    assert np.all(ref == -1)
+    ref, _ = check(CL, P0[:500], colours(500), 3.0, 0)                 # every point core
+    assert ref.min() == 0 and ref.max() > 0
+
+
+def test_mid_size_view(CL):
+    (P, C), _ = oracle_cloud((640, 360), 25.0, 1, 1)
+    assert len(P) == 136897
+    ref, _ = check(CL, P, C, 4.0, 16)
+    assert CR.info(ref) == [4, 2, 48965, 562]
+
+
+def test_determinism_and_chaining(CL, base):
+    """Two runs give equal label bits; Reconstructor cloud -> radius -> statistical -> largest
+    cluster without a host copy equals the chain through host arrays and the restatements."""
+    from structured_light_for_3d_model_replication_amd import engine as E
+    P, C = base[2]
+    a = CL.dbscan_labels(dev(P), 4.0, 12)[0].cpu().numpy()
+    b = CL.dbscan_labels(dev(P), 4.0, 12)[0].cpu().numpy()
+    assert np.array_equal(a, b)
+
+    (Po, Co), (rig, v) = oracle_cloud((192, 128), 25.0, 1, 1)
+    frames = E.DeviceFrames(list(v.frames), v.texture)
+    eng = E.Reconstructor(frames.height, frames.width)
+    dc = E.DeviceCalib(rig.tables(), frames.height, frames.width)
+    cfg = E.DecodeConfig(1920, 1080, 11, 10, "otsu")
+
+    def chain(pc):
+        return CL.largest_cluster(CL.statistical_outlier(CL.radius_outlier(pc, NB, RADIUS), KNN, RATIO), 10.0, 16).numpy()
+
+    Pd, Cd = chain(CL.PointCloud.from_cloud(eng.reconstruct(frames, cfg, dc, row_mode=1, xyz_f64=True)))
+    Ph, Ch = chain(CL.PointCloud(Po, Co))
+    assert np.array_equal(bits(Pd), bits(Ph)) and np.array_equal(Cd, Ch)
+    k1, _ = R.radius_filter(Po, NB, RADIUS)
+    k2, _, _ = R.statistical_filter(Po[k1], KNN, RATIO)
+    P2, C2 = Po[k1][k2], Co[k1][k2]
+    ref = CR.closed_labels(CR.neighbour_graph(P2, 10.0), 16)
+    k3 = ref == CR.largest(ref)[0]
+    assert 0 < k3.sum() < len(P2)
+    assert np.array_equal(bits(Ph), bits(P2[k3])) and np.array_equal(Ch, C2[k3])
+
+
+def test_status_and_arguments(CL, base):
+    import torch
+    from structured_light_for_3d_model_replication_amd import _native as N
+    P0, C0 = base[1]
+    P = P0[:2000].copy()
+    P[777, 1] = np.nan
+    with pytest.raises(ValueError, match="NaN"):
+        CL.dbscan_labels(dev(P), 10.0, 16)
+    with pytest.raises(ValueError, match="2\\^21"):
+        CL.dbscan_labels(dev(np.array([[0.0, 0, 0], [1.0, 0, 0]])), 1e-9, 1)
+    check(CL, P0, C0, 10.0, 16)                                         # a normal call still passes
+
+    L = N.lib()
+    buf = torch.zeros(1 << 16, dtype=torch.uint8, device="cuda")
+    p = ctypes.c_void_p(buf.data_ptr())
+    nb = buf.numel()
+    assert L.slg_dbscan(p, 0, 1.0, 1, p, nb, p, None, None, None) == N.SLG_ERR_INVALID
+    assert L.slg_dbscan(p, -3, 1.0, 1, p, nb, p, None, None, None) == N.SLG_ERR_INVALID
+    assert L.slg_dbscan(p, 4, 0.0, 1, p, nb, p, None, None, None) == N.SLG_ERR_INVALID
+    assert L.slg_dbscan(p, 4, -1.0, 1, p, nb, p, None, None, None) == N.SLG_ERR_INVALID
+    assert L.slg_dbscan(p, 4, float("nan"), 1, p, nb, p, None, None, None) == N.SLG_ERR_INVALID
+    assert L.slg_dbscan(p, 4, 1.0, -1, p, nb, p, None, None, None) == N.SLG_ERR_INVALID
+    assert L.slg_dbscan(None, 4, 1.0, 1, p, nb, p, None, None, None) == N.SLG_ERR_INVALID
+    assert L.slg_dbscan(p, 4, 1.0, 1, p, nb, None, None, None, None) == N.SLG_ERR_INVALID
+    assert L.slg_dbscan(p, 4, 1.0, 1, None, nb, p, None, None, None) == N.SLG_ERR_INVALID
+    assert L.slg_dbscan(p, (1 << 30) + 1, 1.0, 1, p, nb, p, None, None, None) == N.SLG_ERR_UNSUPPORTED
+
+    empty = CL.PointCloud(np.zeros((0, 3)), np.zeros((0, 3), np.uint8))
+    with pytest.raises(ValueError, match="Point cloud is empty."):
+        CL.largest_cluster(empty, 5.0, 200)
+    with pytest.raises(ValueError, match="Point cloud is empty."):
+        CL.dbscan_labels(torch.zeros((0, 3), dtype=torch.float64, device="cuda"), 5.0, 200)
+
+
+def test_drop_in_on_files(CL, base, tmp_path, capsys):
+    from structured_light_for_3d_model_replication_amd.processing import ProcessingLogic
+    P, C = base[1]
+    src, dst, none = (str(tmp_path / n) for n in ("in.ply", "out.ply", "none.ply"))
+    ProcessingLogic._save_ply(P, C, src)
+    Pr, Cr = CL.read_ply(src)
+    ref = CR.closed_labels(CR.neighbour_graph(Pr, 10.0), 16)
+    keep = ref == CR.largest(ref)[0]
+    assert ProcessingLogic.keep_largest_cluster(src, dst, eps=10.0, min_points=16) is None
+    out = ProcessingLogic.keep_largest_cluster(src, dst, 10.0, 16, return_obj=True)
+    assert np.array_equal(bits(out.numpy()[0]), bits(Pr[keep])) and np.array_equal(out.numpy()[1], Cr[keep])
+    Pf, Cf = CL.read_ply(dst)
+    assert np.array_equal(Pf, Pr[keep]) and np.array_equal(Cf, Cr[keep])
+    log = capsys.readouterr().out
+    assert "[Cluster] Processing..." in log and f"[Cluster] Kept largest group: {int(keep.sum())} pts" in log
+    assert f"[Cluster] Saved to {dst}" in log
+
+    pc = CL.PointCloud(Pr, Cr)                                         # the defaults: all noise
+    assert ProcessingLogic.keep_largest_cluster(pc, none, return_obj=True) is pc
+    assert ProcessingLogic.keep_largest_cluster(pc, none) is None
+    import os
+    assert not os.path.exists(none)
+    log = capsys.readouterr().out
+    assert "Kept largest group" not in log and "Saved" not in log
+    with pytest.raises(ValueError, match="Point cloud is empty."):
+        ProcessingLogic.keep_largest_cluster(CL.PointCloud(np.zeros((0, 3))), return_obj=True)

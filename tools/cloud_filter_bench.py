@@ -7,6 +7,13 @@ HIP events around mask + select (status and count are read once per call, as a u
 Beside that, the same rules on the host: tests/cloud_ref.py over scipy's cKDTree with
 ``workers`` threads, on the same points, in the same run.  The two masks are compared.
 
+The cluster step (DBSCAN + largest cluster, timed around labels + select) runs on the same cloud at
+the reference's defaults (eps 5.0, min_points 200) and at a second setting that splits the view
+into many clusters (``--cluster-multi``, default 1.0 16); the host side is the closed form of
+tests/cluster_ref.py folded block by block (the whole graph of a 1080p view does not fit in
+memory), and the labels are compared.  Read the cluster times against the radius filter's of the
+same run: the cluster step is the radius count plus two more neighbourhood walks.
+
 Prints one JSON line.
 """
 from __future__ import annotations
@@ -29,6 +36,8 @@ def main():
     ap.add_argument("--row-mode", type=int, default=1)
     ap.add_argument("--cam", type=int, nargs=2, default=(1920, 1080))
     ap.add_argument("--workers", type=int, default=16)
+    ap.add_argument("--cluster-multi", type=float, nargs=2, default=(1.0, 16), metavar=("EPS", "MIN_POINTS"),
+                    help="the second cluster setting (one that splits the view into several clusters)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cKDTree side")
     args = ap.parse_args()
 
@@ -72,6 +81,14 @@ def main():
                           "whole_cloud_points": CL.far_count(pc.xyz.device)}
     _, ms = timed(lambda: CL.statistical_mask(pc.xyz, 20, 2.0))
     res["statistical"]["device_mask_only_ms"] = ms
+    clusters = {"cluster": (5.0, 200), "cluster_multi": tuple(args.cluster_multi)}
+    labels = {}
+    for name, (eps, mp) in clusters.items():
+        (big, _), ms = timed(lambda: CL.largest_cluster(pc, eps, int(mp), return_index=True))
+        (labels[name], _, info), ms_l = timed(lambda: CL.dbscan_labels(pc.xyz, eps, int(mp)))
+        info = info.cpu().tolist()
+        res[name] = {"eps": eps, "min_points": int(mp), "kept": len(big), "clusters": info[0], "largest_label": info[1],
+                     "largest_count": info[2], "noise": info[3], "device_ms": ms, "device_labels_only_ms": ms_l}
 
     if not args.no_cpu:
         import cloud_ref as R
@@ -83,6 +100,16 @@ def main():
         t2 = time.perf_counter()
         res["cpu"] = {"what": f"tests/cloud_ref.py, scipy cKDTree(workers={args.workers})",
                       "radius_ms": (t1 - t0) * 1e3, "statistical_ms": (t2 - t1) * 1e3}
+        import cluster_ref as CR
+        for name, (eps, mp) in clusters.items():
+            t0 = time.perf_counter()
+            ref = CR.closed_labels_blocked(P, eps, int(mp), workers=args.workers)
+            res["cpu"][name + "_ms"] = (time.perf_counter() - t0) * 1e3
+            print(f"[cpu] {name} done", file=sys.stderr, flush=True)
+            res[name]["labels_equal_cpu"] = bool(np.array_equal(labels[name].cpu().numpy(), ref))
+            res[name]["speedup_vs_cpu"] = res["cpu"][name + "_ms"] / (sum(res[name]["device_ms"]) / args.steps)
+        res["cpu"]["cluster_what"] = (f"tests/cluster_ref.py closed_labels_blocked, scipy cKDTree(workers={args.workers}) "
+                                      "+ csgraph.connected_components")
         res["radius"]["mask_equal_cpu"] = bool(np.array_equal(rad_idx.cpu().numpy(), np.flatnonzero(keep_r)))
         res["statistical"]["mask_equal_cpu"] = bool(np.array_equal(sta_idx.cpu().numpy(), np.flatnonzero(keep_s)))
         res["radius"]["speedup_vs_cpu"] = res["cpu"]["radius_ms"] / (sum(res["radius"]["device_ms"]) / args.steps)
