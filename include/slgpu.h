@@ -473,6 +473,55 @@ int32_t slg_dbscan(const double *xyz, int64_t n, double eps, int32_t min_points,
                    int32_t *info_out,            /* [4] or NULL: n_clusters, largest_label, largest_count, n_noise */
                    void *stream);
 
+/* ---- Voxel down-sample, normals, orientation and centroid on the device cloud
+ * (csrc/cloud_filter.hip): the Open3D operations of the tail of merge_pro_360
+ * (server/processing.py:605-628) and of the front of both meshing methods (:653-670, :804-837).
+ * Open3D's published rules restated, fp64, no floating-point atomics: the same input gives the
+ * same bits.  ws, where a function takes one, is slg_filter_ws_bytes(n, 0) bytes; asynchronous on
+ * `stream`, no host synchronisation; the status word at the front of ws as for the filters
+ * (slg_voxel_downsample and slg_estimate_normals set it).
+ *
+ *   slg_voxel_downsample    <- PointCloud.voxel_down_sample(voxel_size)
+ * vmin = min_bound - voxel_size * 0.5 per axis; a point's voxel is floor((p - vmin) / voxel_size)
+ * (IEEE subtraction and division).  A voxel's point is, per axis, the sum of its members'
+ * coordinates taken left to right in ascending input index, divided by their number; its colour
+ * is per channel (2 * sum + count) / (2 * count) in integers (the exact mean, half up).  Voxels
+ * come out in ascending order of their smallest member index (our rule: Open3D's order is that of
+ * a hash map).  xyz_out float64 [n][3]; bgr / bgr_out uint8 [n][3] or NULL; first_index_out
+ * int64 [n] (the smallest member index) and count_out int32 [n] or NULL; *m_out (DEVICE int64) =
+ * the number of voxels, which is how many entries of each output are written.  A span of 2^21 or
+ * more voxels on an axis sets SLG_FILTER_BAD_EXTENT.
+ *
+ *   slg_estimate_normals    <- PointCloud.estimate_normals(KDTreeSearchParamHybrid(radius, max_nn))
+ * Neighbours of i: all points in ascending (d2, input index) order, i included; the first
+ * min(max_nn, n) of them; of those the ones with d2 < radius * radius (strict).  m = their number.
+ * Nine sums over them in that order (x, y, z, xx, xy, xz, yy, yz, zz), each divided by m, then
+ * cov_ab = E[ab] - E[a] * E[b].  The normal is the unit eigenvector of cov's smallest eigenvalue,
+ * signed so that the first non-zero of (nz, ny, nx) is positive; (0, 0, 1) when m < 3 or cov is
+ * identically zero.  normals_out float64 [n][3]; cov_out float64 [n][6] (xx, xy, xz, yy, yz, zz)
+ * and m_out int32 [n] may be NULL.  3 <= max_nn <= 64 (SLG_ERR_UNSUPPORTED above).  Afterwards the
+ * int32 at byte 8 of ws counts the points that left the grid walk for the whole-cloud kernel.
+ *
+ *   slg_orient_normals      <- orient_normals_towards_camera_location(location) [then * -1.0]
+ * normals[i] is negated when normals[i] . (location - xyz[i]) < 0; with outward != 0 every normal
+ * is negated afterwards.  `location` is DEVICE float64 [3].  In place.
+ *
+ *   slg_cloud_centroid      <- PointCloud.get_center() / points.mean(axis=0)
+ * centroid_out (DEVICE float64 [3]) = per-axis sum / n, the sum a fixed tree over the input order.
+ *
+ * SLG_ERR_INVALID for n <= 0, a size that is not finite and > 0, max_nn < 3 or a NULL required
+ * buffer; SLG_ERR_UNSUPPORTED above 2^30 points. */
+int32_t slg_voxel_downsample(const double *xyz, const uint8_t *bgr, int64_t n, double voxel_size,
+                             void *ws, int64_t ws_bytes, double *xyz_out, uint8_t *bgr_out,
+                             int64_t *first_index_out, int32_t *count_out, int64_t *m_out, void *stream);
+int32_t slg_estimate_normals(const double *xyz, int64_t n, double radius, int32_t max_nn,
+                             void *ws, int64_t ws_bytes, double *normals_out, double *cov_out,
+                             int32_t *m_out, void *stream);
+int32_t slg_orient_normals(const double *xyz, double *normals, int64_t n, const double *location,
+                           int32_t outward, void *stream);
+int32_t slg_cloud_centroid(const double *xyz, int64_t n, void *ws, int64_t ws_bytes,
+                           double *centroid_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,6 +150,10 @@ EXPORTS = {
     "slg_statistical_outlier": (c_i32, [c_vp, c_i64, c_i32, c_dbl, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "slg_cloud_select": (c_i32, [c_vp, c_vp, c_i64, c_vp, ctypes.POINTER(Cloud), c_vp, c_vp, c_vp]),
     "slg_dbscan": (c_i32, [c_vp, c_i64, c_dbl, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "slg_voxel_downsample": (c_i32, [c_vp, c_vp, c_i64, c_dbl, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "slg_estimate_normals": (c_i32, [c_vp, c_i64, c_dbl, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "slg_orient_normals": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i32, c_vp]),
+    "slg_cloud_centroid": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
 }
 FILTER_BAD_NONFINITE, FILTER_BAD_EXTENT = 1, 2
 GATHER_ID_BYTES = 128

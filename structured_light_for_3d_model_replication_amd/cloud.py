@@ -8,8 +8,14 @@ steps of the reference's cleanup tab (``ProcessingLogic.remove_radius_outlier``,
 trip through the host.  Semantics: ``include/slgpu.h`` and DESIGN.md §9 (Open3D's published rules
 restated; parity with an installed Open3D is unpinned).
 
+The same grid carries the Open3D steps of the merge tail and of the front of both meshing methods
+(``server/processing.py:605-628``, ``:653-670``, ``:804-837``): :func:`voxel_down_sample`,
+:func:`uniform_down_sample`, :func:`estimate_normals`, :func:`orient_normals_towards` and
+:func:`centroid`.
+
 The PLY reader takes exactly the file ``ProcessingLogic._save_ply`` writes (``ply.header``): ASCII,
-``x y z red green blue``.  Anything else raises ``ValueError`` saying what differs.
+``x y z red green blue``, or the same with ``nx ny nz`` after ``z`` (a cloud with normals).
+Anything else raises ``ValueError`` saying what differs.
 """
 from __future__ import annotations
 
@@ -28,8 +34,14 @@ MAX_NEIGHBORS = 64          # kMaxK of csrc/cloud_filter.hip
 _HEADER_TAIL = PLY.header(0).decode().split("\n")[3:-1]      # the property lines + end_header
 
 
-def read_ply(path):
-    """``(P float64 [n, 3], C uint8 [n, 3] BGR)`` of an ASCII PLY in ``_save_ply``'s layout."""
+_NORMAL_LINES = ["property float nx", "property float ny", "property float nz"]
+_HEADER_TAIL_NORMALS = _HEADER_TAIL[:3] + _NORMAL_LINES + _HEADER_TAIL[3:]
+
+
+def read_ply(path, normals: bool = False):
+    """``(P float64 [n, 3], C uint8 [n, 3] BGR)`` of an ASCII PLY in ``_save_ply``'s layout, or in
+    the layout with normals (``x y z nx ny nz red green blue``).  With ``normals=True`` the
+    result is ``(P, C, normals float64 [n, 3] or None)``."""
     with open(path, "rb") as f:
         data = f.read()
     end = data.find(b"end_header\n")
@@ -45,31 +57,55 @@ def read_ply(path):
     if len(parts) != 3 or parts[:2] != ["element", "vertex"] or not parts[2].isdigit():
         raise ValueError(f"{path}: expected 'element vertex <n>' as the third header line, got {lines[2]!r}")
     n = int(parts[2])
-    if lines[3:] != _HEADER_TAIL:
+    if lines[3:] == _HEADER_TAIL:
+        width = 6
+    elif lines[3:] == _HEADER_TAIL_NORMALS:
+        width = 9
+    else:
         raise ValueError(f"{path}: the vertex layout must be exactly {_HEADER_TAIL[:-1]} "
-                         f"(what _save_ply writes), got {lines[3:-1]}")
+                         f"(what _save_ply writes) or {_HEADER_TAIL_NORMALS[:-1]} (with normals), "
+                         f"got {lines[3:-1]}")
     body = data[end + len(b"end_header\n"):]
     try:
         vals = np.array(body.split(), dtype=np.float64)
     except ValueError as e:
         raise ValueError(f"{path}: a vertex line holds something that is not a number ({e})") from None
-    if vals.size != 6 * n:
-        raise ValueError(f"{path}: header promises {n} vertices of 6 values, body holds {vals.size} values")
-    vals = vals.reshape(n, 6)
-    rgb = vals[:, 3:]
+    if vals.size != width * n:
+        raise ValueError(f"{path}: header promises {n} vertices of {width} values, body holds {vals.size} values")
+    vals = vals.reshape(n, width)
+    rgb = vals[:, width - 3:]
     if n and not (np.all(rgb == np.floor(rgb)) and rgb.min() >= 0 and rgb.max() <= 255):
         raise ValueError(f"{path}: colours must be integers 0..255")
-    return np.ascontiguousarray(vals[:, :3]), np.ascontiguousarray(rgb[:, ::-1].astype(np.uint8))
+    P, C = np.ascontiguousarray(vals[:, :3]), np.ascontiguousarray(rgb[:, ::-1].astype(np.uint8))
+    if not normals:
+        return P, C
+    return P, C, (np.ascontiguousarray(vals[:, 3:6]) if width == 9 else None)
+
+
+def write_ply_normals(path, points, colors, normals) -> None:
+    """The layout with normals on the host: ``_save_ply``'s header with the three normal
+    properties after ``z``, positions as ``%.4f``, normals as ``%.6f``, BGR swapped to RGB."""
+    P = np.asarray(points, np.float64).reshape(-1, 3)
+    Nrm = np.asarray(normals, np.float64).reshape(-1, 3)
+    C = np.asarray(colors, np.uint8).reshape(-1, 3)
+    if not len(P) == len(Nrm) == len(C):
+        raise ValueError("points, normals and colors differ in length")
+    head = PLY.header(len(P)).decode().split("\n")
+    head = head[:6] + _NORMAL_LINES + head[6:]
+    with open(path, "wb") as f:
+        f.write("\n".join(head).encode())
+        np.savetxt(f, np.hstack([P, Nrm, C[:, ::-1].astype(np.float64)]),
+                   fmt="%.4f %.4f %.4f %.6f %.6f %.6f %d %d %d")
 
 
 class PointCloud:
-    """A cloud in HBM: ``xyz`` float64 ``[n, 3]`` and ``bgr`` uint8 ``[n, 3]`` (an empty cloud
-    holds empty host tensors and needs no device).
+    """A cloud in HBM: ``xyz`` float64 ``[n, 3]``, ``bgr`` uint8 ``[n, 3]`` and ``normals``
+    float64 ``[n, 3]`` or ``None`` (an empty cloud holds empty host tensors and needs no device).
 
     Build it from ``(P, C)`` arrays or tensors, from an ``engine.Cloud`` (:meth:`from_cloud`, the
     points stay on the device) or from a PLY written by ``_save_ply`` (:meth:`from_file`)."""
 
-    def __init__(self, points, colors=None, device=None):
+    def __init__(self, points, colors=None, device=None, normals=None):
         def as_tensor(a, dt, np_dt):
             if isinstance(a, torch.Tensor):
                 return a.reshape(-1, 3).to(dt)
@@ -86,6 +122,12 @@ class PointCloud:
             dev = device or (xyz.device if xyz.is_cuda else E.default_device())
             xyz, bgr = xyz.to(dev).contiguous(), bgr.to(dev).contiguous()
         self.xyz, self.bgr = xyz, bgr
+        self.normals = None
+        if normals is not None:
+            nrm = as_tensor(normals, torch.float64, np.float64)
+            if len(nrm) != len(xyz):
+                raise ValueError("points and normals differ in length")
+            self.normals = nrm.to(xyz.device).contiguous()
 
     @classmethod
     def from_cloud(cls, cloud: "E.Cloud") -> "PointCloud":
@@ -98,10 +140,14 @@ class PointCloud:
 
     @classmethod
     def from_file(cls, path) -> "PointCloud":
-        return cls(*read_ply(path))
+        P, C, nrm = read_ply(path, normals=True)
+        return cls(P, C, normals=nrm)
 
     def has_points(self) -> bool:
         return len(self) > 0
+
+    def has_normals(self) -> bool:
+        return self.normals is not None and len(self) > 0
 
     def __len__(self) -> int:
         return int(self.xyz.shape[0])
@@ -111,8 +157,12 @@ class PointCloud:
         return self.xyz.cpu().numpy(), self.bgr.cpu().numpy()
 
     def save(self, path) -> None:
-        """ASCII PLY as ``_save_ply`` writes it."""
-        PLY.write_ascii(path, *self.numpy())
+        """ASCII PLY as ``_save_ply`` writes it; a cloud with normals is written by the host
+        writer in the layout with normals (:func:`write_ply_normals`)."""
+        if self.normals is None:
+            PLY.write_ascii(path, *self.numpy())
+        else:
+            write_ply_normals(path, *self.numpy(), self.normals.cpu().numpy())
 
 
 def as_point_cloud(obj) -> PointCloud:
@@ -156,12 +206,13 @@ def _check_status(ws: torch.Tensor, what: str) -> None:
     if status & N.FILTER_BAD_NONFINITE:
         raise ValueError(f"{what}: the cloud holds a NaN or infinite coordinate")
     if status & N.FILTER_BAD_EXTENT:
-        raise ValueError(f"{what}: the cloud spans 2^21 or more cells of the radius on an axis")
+        raise ValueError(f"{what}: the cloud spans 2^21 or more cells of the radius or voxel size on an axis")
 
 
 def far_count(device) -> int:
-    """Points the last :func:`statistical_mask` on ``device`` sent to the whole-cloud kernel (the
-    ring walk reached its cap): the int32 at byte 8 of the workspace.  A test hook."""
+    """Points the last :func:`statistical_mask` or :func:`normal_covariances` on ``device`` sent
+    to the whole-cloud kernel (the ring walk reached its cap): the int32 at byte 8 of the
+    workspace.  A test hook."""
     return int(_WS[device][8:12].view(torch.int32).item())
 
 
@@ -223,7 +274,8 @@ def _raise(rc: int) -> None:
 
 
 def select(pc: PointCloud, keep: torch.Tensor, stream=None):
-    """``(PointCloud of the points with keep != 0 in input order, their indices int64)``."""
+    """``(PointCloud of the points with keep != 0 in input order, their indices int64)``.  The
+    result has no normals."""
     n = len(pc)
     dev = pc.xyz.device
     with torch.cuda.device(dev):
@@ -239,7 +291,8 @@ def select(pc: PointCloud, keep: torch.Tensor, stream=None):
 
 def radius_outlier(pc, nb_points: int, radius: float, return_index: bool = False):
     """Open3D ``remove_radius_outlier`` + ``select_by_index`` on the device: a new ``PointCloud``
-    of the points with more than ``nb_points`` points (itself included) closer than ``radius``."""
+    of the points with more than ``nb_points`` points (itself included) closer than ``radius``.
+    Normals are not carried over: the result has none."""
     pc = as_point_cloud(pc)
     if not pc.has_points():
         raise ValueError("Point cloud is empty.")
@@ -250,7 +303,7 @@ def radius_outlier(pc, nb_points: int, radius: float, return_index: bool = False
 
 def statistical_outlier(pc, nb_neighbors: int, std_ratio: float, return_index: bool = False):
     """Open3D ``remove_statistical_outlier`` + ``select_by_index`` on the device
-    (``nb_neighbors`` <= 64)."""
+    (``nb_neighbors`` <= 64).  Normals are not carried over: the result has none."""
     pc = as_point_cloud(pc)
     if not pc.has_points():
         raise ValueError("Point cloud is empty.")
@@ -263,7 +316,8 @@ def largest_cluster(pc, eps: float, min_points: int, return_index: bool = False)
     """Open3D ``cluster_dbscan`` + the largest-label pick of ``keep_largest_cluster`` +
     ``select_by_index`` on the device: a new ``PointCloud`` of the largest cluster's points in
     input order (the lowest label among equally large ones).  When every point is noise the input
-    cloud itself comes back, with indices ``arange(n)``."""
+    cloud itself comes back, with indices ``arange(n)``.  Normals are not carried over: a
+    selected result has none."""
     pc = as_point_cloud(pc)
     if not pc.has_points():
         raise ValueError("Point cloud is empty.")
@@ -272,3 +326,105 @@ def largest_cluster(pc, eps: float, min_points: int, return_index: bool = False)
         return (pc, torch.arange(len(pc), dtype=torch.int64, device=pc.xyz.device)) if return_index else pc
     out, idx = select(pc, keep)
     return (out, idx) if return_index else out
+
+
+# ----------------------------------------------------------------------------- merge / mesh tail
+def voxel_down_sample(pc, voxel_size: float, return_index: bool = False, stream=None):
+    """Open3D ``voxel_down_sample`` on the device: one point per occupied voxel of
+    ``floor((p - (min_bound - voxel_size / 2)) / voxel_size)``, the mean of its members summed left
+    to right in ascending index; colours the exact mean rounded half up; voxels in ascending order
+    of their smallest member index.  The result has no normals.  With ``return_index``:
+    ``(cloud, first_index int64 [m], count int32 [m])``."""
+    pc = as_point_cloud(pc)
+    if not pc.has_points():
+        raise ValueError("Point cloud is empty.")
+    xyz = _check_xyz(pc.xyz)
+    n, dev = xyz.shape[0], xyz.device
+    with torch.cuda.device(dev):
+        ws = _workspace(n, 0, dev)
+        oxyz = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        obgr = torch.empty((n, 3), dtype=torch.uint8, device=dev)
+        first = torch.empty(n, dtype=torch.int64, device=dev)
+        count = torch.empty(n, dtype=torch.int32, device=dev)
+        m = torch.zeros(1, dtype=torch.int64, device=dev)
+        _raise(N.lib().slg_voxel_downsample(E._vp(xyz), E._vp(pc.bgr), n, float(voxel_size), E._vp(ws), ws.numel(),
+                                            E._vp(oxyz), E._vp(obgr), E._vp(first), E._vp(count), E._vp(m),
+                                            E._stream(stream)))
+        _check_status(ws, "voxel_down_sample")
+        m = int(m.item())
+    out = PointCloud(oxyz[:m], obgr[:m])
+    return (out, first[:m], count[:m]) if return_index else out
+
+
+def uniform_down_sample(pc, every_k: int):
+    """Open3D ``uniform_down_sample``: the points ``0, k, 2k, ...`` (normals too, when present)."""
+    pc = as_point_cloud(pc)
+    every_k = int(every_k)
+    if every_k < 1:
+        raise ValueError("every_k must be >= 1")
+    return PointCloud(pc.xyz[::every_k].contiguous(), pc.bgr[::every_k].contiguous(),
+                      normals=None if pc.normals is None else pc.normals[::every_k].contiguous())
+
+
+def normal_covariances(xyz: torch.Tensor, radius: float, max_nn: int, stream=None):
+    """``(cov float64 [n, 6] = xx, xy, xz, yy, yz, zz, m int32 [n], normals float64 [n, 3])`` on
+    the device: the hybrid search's neighbour count, their covariance and the normal."""
+    xyz = _check_xyz(xyz)
+    n, dev = xyz.shape[0], xyz.device
+    with torch.cuda.device(dev):
+        ws = _workspace(n, 0, dev)
+        nrm = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        cov = torch.empty((n, 6), dtype=torch.float64, device=dev)
+        m = torch.empty(n, dtype=torch.int32, device=dev)
+        _raise(N.lib().slg_estimate_normals(E._vp(xyz), n, float(radius), int(max_nn), E._vp(ws), ws.numel(),
+                                            E._vp(nrm), E._vp(cov), E._vp(m), E._stream(stream)))
+        _check_status(ws, "estimate_normals")
+    return cov, m, nrm
+
+
+def estimate_normals(pc, radius: float, max_nn: int = 30):
+    """Open3D ``estimate_normals(KDTreeSearchParamHybrid(radius, max_nn))`` on the device
+    (``3 <= max_nn <= 64``): a ``PointCloud`` sharing ``xyz`` / ``bgr`` with ``normals`` set."""
+    pc = as_point_cloud(pc)
+    if not pc.has_points():
+        raise ValueError("Point cloud is empty.")
+    _, _, nrm = normal_covariances(pc.xyz, radius, max_nn)
+    return PointCloud(pc.xyz, pc.bgr, normals=nrm)
+
+
+def centroid(pc, stream=None) -> torch.Tensor:
+    """Per-axis mean of the points, float64 ``[3]`` on the device (``get_center()``)."""
+    pc = as_point_cloud(pc)
+    if not pc.has_points():
+        raise ValueError("Point cloud is empty.")
+    xyz = _check_xyz(pc.xyz)
+    n, dev = xyz.shape[0], xyz.device
+    with torch.cuda.device(dev):
+        ws = _workspace(n, 0, dev)
+        out = torch.empty(3, dtype=torch.float64, device=dev)
+        _raise(N.lib().slg_cloud_centroid(E._vp(xyz), n, E._vp(ws), ws.numel(), E._vp(out), E._stream(stream)))
+    return out
+
+
+def orient_normals_towards(pc, location, outward: bool = False, stream=None):
+    """Open3D ``orient_normals_towards_camera_location(location)``: a normal with
+    ``normal . (location - p) < 0`` is negated; ``outward`` then negates every normal (the
+    reference's ``* -1.0``).  ``location``: three numbers or a device tensor.  A new ``PointCloud``
+    sharing ``xyz`` / ``bgr``."""
+    pc = as_point_cloud(pc)
+    if not pc.has_normals():
+        raise ValueError("the cloud has no normals")
+    xyz = _check_xyz(pc.xyz)
+    n, dev = xyz.shape[0], xyz.device
+    if isinstance(location, torch.Tensor):
+        loc = location.to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+    else:
+        loc = torch.tensor([float(v) for v in np.asarray(location, np.float64).reshape(-1)], dtype=torch.float64,
+                           device=dev)
+    if loc.numel() != 3:
+        raise ValueError("location must hold three numbers")
+    with torch.cuda.device(dev):
+        nrm = pc.normals.clone()
+        _raise(N.lib().slg_orient_normals(E._vp(xyz), E._vp(nrm), n, E._vp(loc), int(bool(outward)),
+                                          E._stream(stream)))
+    return PointCloud(pc.xyz, pc.bgr, normals=nrm)

@@ -3,9 +3,14 @@
 Same names, signatures, return types and error behaviour as the reference
 (``server/processing.py:27-334``); the arithmetic runs in the HIP kernels of ``libslgpu.so``.
 The reconstruction path is provided, and of the Open3D post-processing methods of the
-reference class (``remove_background`` ... ``mesh_360``, processing.py:336-860) the two
-deterministic neighbour filters, ``remove_outliers`` and ``remove_radius_outlier``, which run
-on the device (``cloud.py``); the rest are out of scope.
+reference class (``remove_background`` ... ``mesh_360``, processing.py:336-860) the
+deterministic neighbour steps, which run on the device (``cloud.py``): ``remove_outliers``,
+``remove_radius_outlier`` and ``keep_largest_cluster``, the post-processing tail of
+``merge_pro_360`` (:605-628: voxel down-sample, uniform sample, outlier removal, normals) as
+``merge_postprocess``, and the normal estimation and radial orientation that open
+``reconstruct_stl`` and ``mesh_360`` (:653-670, :804-837) as ``estimate_oriented_normals``.
+Registration (FPFH, RANSAC, ICP), tangent-plane orientation, Poisson, ball pivoting and RANSAC
+plane removal are out of scope.
 """
 from __future__ import annotations
 
@@ -421,6 +426,63 @@ class ProcessingLogic:
             ProcessingLogic._save_ply(*cleaned_pcd.numpy(), output_path)
             print(f"[Cluster] Saved to {output_path}")
         return cleaned_pcd if return_obj else None
+
+    # --- Merge tail and mesh front (device; cloud.py) ---
+    @staticmethod
+    def merge_postprocess(merged, output_path=None, voxel_size=0.02, outlier_nb=20, outlier_std=2.0,
+                          sample_after=1, final_voxel=0.5, return_obj=False):
+        """The post-processing tail of ``merge_pro_360`` (``server/processing.py:605-628``) on the
+        device; the reference has no stand-alone method for it.  Same order of steps, conditions
+        and print lines: final voxel down-sample when ``final_voxel > 0``, uniform sample when
+        ``sample_after > 1``, statistical outlier removal (``outlier_nb``, ``outlier_std``), normals
+        with ``radius = voxel_size * 2`` and ``max_nn = 30``, then the save.  ``merged``: a path,
+        a ``PointCloud`` or ``(P, C)``.  ``output_path`` is written as ASCII PLY with normals (the
+        reference writes Open3D's binary PLY)."""
+        from . import cloud as CL
+        pcd_combined_down = ProcessingLogic._load_pcd(merged)
+        if not pcd_combined_down.has_points():
+            raise ValueError("Point cloud is empty.")
+        print(f"[Merge 360] Post-processing (Final Voxel: {final_voxel}, Outlier removal)...")
+        if final_voxel > 0:
+            pcd_combined_down = CL.voxel_down_sample(pcd_combined_down, final_voxel)
+            print(f"  After final voxel down-sample: {len(pcd_combined_down)} points")
+        if sample_after > 1:
+            pcd_combined_down = CL.uniform_down_sample(pcd_combined_down, int(sample_after))
+            print(f"  After uniform sample-after: {len(pcd_combined_down)} points")
+        pcd_final = CL.statistical_outlier(pcd_combined_down, outlier_nb, outlier_std)
+        print(f"  After outlier removal: {len(pcd_final)} points (removed {len(pcd_combined_down) - len(pcd_final)})")
+        if pcd_final.has_points():
+            pcd_final = CL.estimate_normals(pcd_final, voxel_size * 2, 30)
+        if output_path:
+            pcd_final.save(output_path)
+            print(f"[Merge 360] Saved merged cloud to {output_path}")
+        return pcd_final if return_obj else None
+
+    @staticmethod
+    def estimate_oriented_normals(input_data, save_normals_path=None, normal_radius=0.1, normal_max_nn=30,
+                                  outward=True, return_obj=False):
+        """Steps 1-2b of ``mesh_360`` in radial mode (``server/processing.py:804-837``) on the
+        device; the reference has no stand-alone method for them.  Normals by the hybrid search
+        (``normal_radius``, ``normal_max_nn``), oriented towards the cloud's centre and then, with
+        ``outward``, negated; with ``normal_radius=10`` this is ``reconstruct_stl``'s centroid
+        branch (``:653-670``).  Raises ``FileNotFoundError`` for a missing path and
+        ``ValueError("Point cloud is empty.")`` as the reference does.  ``save_normals_path`` is
+        written as ASCII PLY with normals."""
+        from . import cloud as CL
+        pcd = ProcessingLogic._load_pcd(input_data)
+        if not pcd.has_points():
+            raise ValueError("Point cloud is empty.")
+        print(f"[360 Mesh] Estimating normals (radius={normal_radius}, max_nn={normal_max_nn})...")
+        pcd = CL.estimate_normals(pcd, normal_radius, normal_max_nn)
+        print(f"[360 Mesh] Re-orienting normals (Mode: radial)...")
+        pcd = CL.orient_normals_towards(pcd, CL.centroid(pcd), outward=outward)
+        if outward:
+            print("[360 Mesh] Radial orientation applied (Outwards).")
+        if save_normals_path:
+            print(f"[360 Mesh] Saving normals point cloud to {save_normals_path}...")
+            pcd.save(save_normals_path)
+            print(f"[360 Mesh] Normals point cloud saved ({len(pcd)} points).")
+        return pcd if return_obj else None
 
 
 def batch_views() -> int:

@@ -1,0 +1,218 @@
+"""Device voxel down-sample (csrc/cloud_filter.hip) against the NumPy restatement
+(normals_ref.py), and the merge tail built on it.
+
+Base inputs: the two smoke-view clouds of test_gpu_cloud_filter.py (12,532 and 25,064 points) at
+a voxel size a few times the point spacing (about 4 mm) and at one where a voxel holds over 1,000
+points."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import normals_ref as NR
+
+pytestmark = pytest.mark.gpu
+
+VOXEL_SMALL, VOXEL_LARGE = 10.0, 100.0
+
+
+@pytest.fixture(scope="module")
+def base():
+    out = {}
+    for rm in (1, 2):
+        P, C = NR.smoke_cloud(rm)
+        out[rm] = dict(P=P, C=C, ref={vs: NR.voxel_down_sample(P, C, vs) for vs in (VOXEL_SMALL, VOXEL_LARGE)})
+        for a in (P, C, *[x for r in out[rm]["ref"].values() for x in r]):
+            a.setflags(write=False)
+    return out
+
+
+@pytest.fixture(scope="module")
+def CL():
+    from structured_light_for_3d_model_replication_amd import cloud
+    return cloud
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint64 if a.dtype == np.float64 else a.dtype)
+
+
+def run(CL, P, C, vs):
+    out, first, count = CL.voxel_down_sample(CL.PointCloud(np.array(P), np.array(C)), vs, return_index=True)
+    Po, Co = out.numpy()
+    assert not out.has_normals()
+    return Po, Co, first.cpu().numpy(), count.cpu().numpy()
+
+
+def check(CL, P, C, vs, ref=None):
+    pts, col, first, count = ref if ref is not None else NR.voxel_down_sample(P, C, vs)
+    Po, Co, fo, co = run(CL, P, C, vs)
+    assert len(Po) == len(pts)
+    assert np.array_equal(co, count) and co.dtype == np.int32
+    assert np.array_equal(fo, first) and fo.dtype == np.int64
+    assert np.all(np.diff(fo) > 0)                       # ascending first index
+    assert np.array_equal(bits(Po), bits(pts))
+    assert np.array_equal(Co, col)
+    return Po, Co, fo, co
+
+
+@pytest.mark.parametrize("vs", [VOXEL_SMALL, VOXEL_LARGE])
+@pytest.mark.parametrize("rm", [1, 2])
+def test_voxel_base(CL, base, rm, vs):
+    b = base[rm]
+    count = b["ref"][vs][3]
+    if vs == VOXEL_SMALL:
+        assert np.mean(count > 1) > 0.5                  # most voxels hold several points
+    else:
+        assert count.max() > 1000                        # the wave kernel's long segments
+    assert count.sum() == len(b["P"])
+    check(CL, b["P"], b["C"], vs, b["ref"][vs])
+
+
+def test_faces_negative_and_decimal_lattice(CL):
+    """Assignments equal NumPy's floor of the IEEE quotient: integer points with voxel faces on
+    the odd integers (min -10, voxel 2: origin -11) and a 0.1-step decimal lattice at voxel 0.3
+    and at voxel 0.2, where the lattice planes fall on voxel faces up to rounding."""
+    g = np.arange(-10, 11, dtype=np.float64)
+    P = np.stack(np.meshgrid(g, g[::3], g[::5], indexing="ij"), -1).reshape(-1, 3)
+    ijk = NR.voxel_coords(P, 2.0)
+    assert np.any((P[:, 0] + 11) % 2 == 0) and P.min() < 0            # points exactly on faces
+    C = (np.arange(len(P) * 3) % 251).astype(np.uint8).reshape(-1, 3)
+    _, _, first, count = check(CL, P, C, 2.0)
+    assert len(first) == len(np.unique(ijk, axis=0))
+    g = 0.3 + 0.1 * np.arange(12)
+    P = np.stack(np.meshgrid(g, g - 7.7, g + 1e3, indexing="ij"), -1).reshape(-1, 3)
+    C = (np.arange(len(P) * 3) % 256).astype(np.uint8).reshape(-1, 3)
+    for vs in (0.3, 0.2):
+        q = (P - NR.voxel_origin(P, vs)) / vs
+        if vs == 0.2:            # quotients (k + 1) / 2: every other lattice plane is a (rounded) voxel face
+            assert np.any((np.abs(q - np.round(q)) < 1e-9) & (q != np.round(q)))    # rounding decides some
+        _, _, first, _ = check(CL, P, C, vs)
+        assert len(first) == len(np.unique(np.floor(q), axis=0))
+
+
+def test_voxel_below_separation_is_identity(CL, base):
+    """Two points of one voxel differ by less than the voxel size on every axis, so they are closer
+    than sqrt(3) voxel sizes: at half the closest pair's separation every point is alone."""
+    from scipy.spatial import cKDTree
+    P, C = base[1]["P"][:4000], base[1]["C"][:4000]
+    sep = cKDTree(P).query(P, k=2)[0][:, 1].min()
+    assert sep > 0
+    Po, Co, first, count = run(CL, P, C, 0.5 * sep)
+    assert np.array_equal(bits(Po), bits(P)) and np.array_equal(Co, C)
+    assert np.array_equal(first, np.arange(len(P))) and np.all(count == 1)
+
+
+def test_one_voxel_for_the_whole_cloud(CL, base):
+    P, C = base[1]["P"], base[1]["C"]
+    Po, Co, first, count = check(CL, P, C, 1e4)
+    assert len(Po) == 1 and first[0] == 0 and count[0] == len(P)
+    seq = np.add.accumulate(P, axis=0)[-1] / len(P)                    # accumulate is sequential
+    assert np.array_equal(bits(Po[0]), bits(seq))
+
+
+@pytest.mark.parametrize("members", [5, 70])
+def test_sum_order_is_left_to_right(CL, members):
+    """A voxel whose left-to-right sum differs in the last bits from its reversed and its pairwise
+    sum (5 members: the lane-per-voxel kernel; 70: the wave kernel), beside a second voxel."""
+    for seed in range(100):
+        rng = np.random.default_rng(seed)
+        V = rng.uniform(0.0, 1.0, (members, 3))
+        ltr = np.add.accumulate(V, axis=0)[-1] / members
+        rev = np.add.accumulate(V[::-1], axis=0)[-1] / members
+        half = members // 2
+        pair = (np.add.accumulate(V[:half], axis=0)[-1] + np.add.accumulate(V[half:], axis=0)[-1]) / members
+        if np.any(bits(ltr) != bits(rev)) and np.any(bits(ltr) != bits(pair)):
+            break
+    else:
+        pytest.fail("no seed gives an order-sensitive sum")
+    other = np.array([[100.2, 100.4, 100.6], [100.7, 100.1, 100.3]])
+    P = np.vstack([other[:1], V, other[1:]])
+    C = np.zeros((len(P), 3), np.uint8)
+    Po, _, first, count = check(CL, P, C, 2.0)
+    assert list(first) == [0, 1] and list(count) == [2, members]
+    assert np.array_equal(bits(Po[1]), bits(ltr))
+
+
+def test_colour_mean_rounds_half_up(CL):
+    P = np.array([[0.1, 0.1, 0.1], [0.2, 0.2, 0.2], [5.1, 5.1, 5.1], [5.2, 5.2, 5.2], [5.3, 5.3, 5.3]])
+    C = np.array([[10, 0, 255], [11, 1, 254], [1, 2, 0], [2, 2, 0], [2, 3, 1]], np.uint8)
+    _, Co, _, count = check(CL, P, C, 1.0)
+    assert list(count) == [2, 3]
+    assert Co.tolist() == [[11, 1, 255], [2, 2, 0]]                    # 10.5 -> 11, 0.5 -> 1, 254.5 -> 255; 5/3 -> 2, 7/3 -> 2, 1/3 -> 0
+
+
+def test_single_point(CL):
+    P, C = np.array([[1.5, -2.5, 3.25]]), np.array([[7, 8, 9]], np.uint8)
+    Po, Co, first, count = check(CL, P, C, 0.5)
+    assert np.array_equal(bits(Po), bits(P)) and np.array_equal(Co, C) and count[0] == 1
+
+
+def test_status_flags_and_arguments(CL, base):
+    import torch
+    from structured_light_for_3d_model_replication_amd import _native as N
+    b = base[1]
+    P = b["P"][:2000].copy()
+    P[777, 1] = np.nan
+    with pytest.raises(ValueError, match="NaN"):
+        CL.voxel_down_sample(CL.PointCloud(P, b["C"][:2000]), 5.0)
+    with pytest.raises(ValueError, match="2\\^21"):
+        CL.voxel_down_sample(CL.PointCloud(np.array([[0.0, 0, 0], [2.2, 0, 0]])), 1e-6)
+    for bad in (0.0, -1.0, float("nan"), float("inf")):
+        with pytest.raises(ValueError):
+            CL.voxel_down_sample(CL.PointCloud(b["P"][:10], b["C"][:10]), bad)
+    with pytest.raises(ValueError, match="empty"):
+        CL.voxel_down_sample(CL.PointCloud(np.zeros((0, 3))), 1.0)
+    L = N.lib()
+    buf = torch.zeros(1 << 16, dtype=torch.uint8, device="cuda")
+    p = ctypes.c_void_p(buf.data_ptr())
+    assert L.slg_voxel_downsample(p, None, 0, 1.0, p, buf.numel(), p, None, None, None, p, None) == N.SLG_ERR_INVALID
+    assert L.slg_voxel_downsample(p, None, 4, 1.0, p, buf.numel(), None, None, None, None, p, None) == N.SLG_ERR_INVALID
+    assert L.slg_voxel_downsample(p, None, (1 << 30) + 1, 1.0, p, buf.numel(), p, None, None, None, p, None) \
+        == N.SLG_ERR_UNSUPPORTED
+    check(CL, b["P"], b["C"], VOXEL_SMALL, b["ref"][VOXEL_SMALL])      # the process goes on
+
+
+def test_uniform_down_sample(CL, base):
+    b = base[1]
+    pc = CL.PointCloud(b["P"], b["C"])
+    for k in (1, 3, 7):
+        Po, Co = CL.uniform_down_sample(pc, k).numpy()
+        Pr, Cr = NR.uniform_down_sample(b["P"], b["C"], k)
+        assert np.array_equal(bits(Po), bits(Pr)) and np.array_equal(Co, Cr)
+
+
+# ------------------------------------------------------------------ the merge tail
+@pytest.mark.parametrize("final_voxel,sample_after", [(10.0, 1), (0, 1), (10.0, 3)])
+def test_merge_postprocess(CL, base, tmp_path, capsys, final_voxel, sample_after):
+    """Two smoke views concatenated through ProcessingLogic.merge_postprocess equal the same chain
+    of cloud.* calls; the print lines are the reference's; the PLY reads back at its precision."""
+    from structured_light_for_3d_model_replication_amd.processing import ProcessingLogic
+    P = np.vstack([base[1]["P"], base[2]["P"]])
+    C = np.vstack([base[1]["C"], base[2]["C"]])
+    dst = str(tmp_path / "merged.ply")
+    out = ProcessingLogic.merge_postprocess((P, C), dst, voxel_size=6.0, outlier_nb=20, outlier_std=2.0,
+                                            sample_after=sample_after, final_voxel=final_voxel, return_obj=True)
+    log = capsys.readouterr().out
+    pc = CL.PointCloud(P, C)
+    if final_voxel > 0:
+        pc = CL.voxel_down_sample(pc, final_voxel)
+        assert f"  After final voxel down-sample: {len(pc)} points\n" in log
+    else:
+        assert "final voxel down-sample" not in log
+    if sample_after > 1:
+        pc = CL.uniform_down_sample(pc, sample_after)
+        assert f"  After uniform sample-after: {len(pc)} points\n" in log
+    else:
+        assert "uniform sample-after" not in log
+    kept = CL.statistical_outlier(pc, 20, 2.0)
+    assert f"  After outlier removal: {len(kept)} points (removed {len(pc) - len(kept)})\n" in log
+    assert f"[Merge 360] Saved merged cloud to {dst}\n" in log
+    want = CL.estimate_normals(kept, 12.0, 30)
+    assert 0 < len(kept) < len(pc) and out.has_normals()
+    assert np.array_equal(bits(out.numpy()[0]), bits(want.numpy()[0])) and np.array_equal(out.numpy()[1], want.numpy()[1])
+    assert np.array_equal(bits(out.normals.cpu().numpy()), bits(want.normals.cpu().numpy()))
+    Pr, Cr, Nr = CL.read_ply(dst, normals=True)
+    assert np.abs(Pr - out.numpy()[0]).max() <= 0.5e-4 + 1e-9 and np.array_equal(Cr, out.numpy()[1])
+    assert np.abs(Nr - out.normals.cpu().numpy()).max() <= 0.5e-6 + 1e-12
+    assert ProcessingLogic.merge_postprocess((P, C), None, voxel_size=6.0, final_voxel=final_voxel) is None

@@ -14,6 +14,13 @@ tests/cluster_ref.py folded block by block (the whole graph of a 1080p view does
 memory), and the labels are compared.  Read the cluster times against the radius filter's of the
 same run: the cluster step is the radius count plus two more neighbourhood walks.
 
+``--voxel SIZE`` and ``--normals RADIUS MAX_NN`` add the voxel down-sample and the normal
+estimation, timed the same way; beside the normals the statistical mask at
+``k = MAX_NN`` is timed in the same run (the same walk without indices, moments and solve).  The
+host side is tests/normals_ref.py, its neighbour lists proposed by cKDTree and ranked by
+(d2, index); positions, colours, counts, ``m`` and ``cov`` are compared, not just timed.
+``--skip-cluster`` leaves the cluster step out.
+
 Prints one JSON line.
 """
 from __future__ import annotations
@@ -39,6 +46,10 @@ def main():
     ap.add_argument("--cluster-multi", type=float, nargs=2, default=(1.0, 16), metavar=("EPS", "MIN_POINTS"),
                     help="the second cluster setting (one that splits the view into several clusters)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cKDTree side")
+    ap.add_argument("--voxel", type=float, metavar="SIZE", help="also time voxel_down_sample at this size")
+    ap.add_argument("--normals", nargs=2, metavar=("RADIUS", "MAX_NN"),
+                    help="also time the normal estimation at this radius and max_nn")
+    ap.add_argument("--skip-cluster", action="store_true", help="leave the cluster step out")
     args = ap.parse_args()
 
     import numpy as np
@@ -81,7 +92,20 @@ def main():
                           "whole_cloud_points": CL.far_count(pc.xyz.device)}
     _, ms = timed(lambda: CL.statistical_mask(pc.xyz, 20, 2.0))
     res["statistical"]["device_mask_only_ms"] = ms
-    clusters = {"cluster": (5.0, 200), "cluster_multi": tuple(args.cluster_multi)}
+    if args.voxel:
+        (vox, vfirst, vcount), ms = timed(lambda: CL.voxel_down_sample(pc, args.voxel, return_index=True))
+        res["voxel"] = {"voxel_size": args.voxel, "voxels": len(vox), "largest": int(vcount.max().item()),
+                        "device_ms": ms}
+    if args.normals:
+        nr, nk = float(args.normals[0]), int(args.normals[1])
+        (ncov, nm, nnrm), ms = timed(lambda: CL.normal_covariances(pc.xyz, nr, nk))
+        res["normals"] = {"radius": nr, "max_nn": nk, "device_ms": ms, "whole_cloud_points": CL.far_count(pc.xyz.device),
+                          "capped": float((nm == nk).double().mean().item()),
+                          "fewer_than_3": int((nm < 3).sum().item())}
+        _, ms_s = timed(lambda: CL.statistical_mask(pc.xyz, nk, 2.0))
+        res["normals"]["statistical_mask_same_k_ms"] = ms_s
+        res["normals"]["ratio_to_statistical_mask"] = sum(ms) / sum(ms_s)
+    clusters = {} if args.skip_cluster else {"cluster": (5.0, 200), "cluster_multi": tuple(args.cluster_multi)}
     labels = {}
     for name, (eps, mp) in clusters.items():
         (big, _), ms = timed(lambda: CL.largest_cluster(pc, eps, int(mp), return_index=True))
@@ -100,6 +124,35 @@ def main():
         t2 = time.perf_counter()
         res["cpu"] = {"what": f"tests/cloud_ref.py, scipy cKDTree(workers={args.workers})",
                       "radius_ms": (t1 - t0) * 1e3, "statistical_ms": (t2 - t1) * 1e3}
+        if args.voxel or args.normals:
+            import normals_ref as NR
+            C = pc.bgr.cpu().numpy()
+
+            def same(a, b):
+                return bool(np.array_equal(np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b).view(np.uint64)))
+        if args.voxel:
+            t0 = time.perf_counter()
+            pts, col, first, count = NR.voxel_down_sample(P, C, args.voxel)
+            res["cpu"]["voxel_ms"] = (time.perf_counter() - t0) * 1e3
+            Pv, Cv = vox.numpy()
+            res["voxel"]["equal_cpu"] = bool(len(Pv) == len(pts) and same(Pv, pts) and np.array_equal(Cv, col)
+                                             and np.array_equal(vfirst.cpu().numpy(), first)
+                                             and np.array_equal(vcount.cpu().numpy(), count))
+            res["voxel"]["speedup_vs_cpu"] = res["cpu"]["voxel_ms"] / (sum(res["voxel"]["device_ms"]) / args.steps)
+        if args.normals:
+            t0 = time.perf_counter()
+            idx, dd, resolved = NR.neighbour_lists_tree(P, nk, workers=args.workers)
+            cov, m, nrm = NR.estimate_normals(P, nr, nk, (idx, dd))
+            res["cpu"]["normals_ms"] = (time.perf_counter() - t0) * 1e3
+            dcov, dm, dn = ncov.cpu().numpy(), nm.cpu().numpy(), nnrm.cpu().numpy()
+            ok = resolved & (m >= 3) & cov.any(1)
+            res["normals"].update({
+                "unresolved_ties_cpu": int((~resolved).sum()),
+                "m_equal_cpu": bool(np.array_equal(dm[resolved], m[resolved])),
+                "cov_equal_cpu": same(dcov[resolved], cov[resolved]),
+                "normals_equal_cpu": same(dn[resolved], nrm[resolved]),
+                "max_rayleigh_excess": float(NR.rayleigh_excess(cov[ok], dn[ok]).max()) if ok.any() else 0.0,
+                "speedup_vs_cpu": res["cpu"]["normals_ms"] / (sum(res["normals"]["device_ms"]) / args.steps)})
         import cluster_ref as CR
         for name, (eps, mp) in clusters.items():
             t0 = time.perf_counter()
