@@ -409,8 +409,8 @@ int32_t slg_gather_destroy(slg_gather_comm *comm);
 int32_t slg_gatherv_plan(int32_t n_ranks, int32_t rank, int32_t root, int64_t send_bytes,
                          const int64_t *recv_bytes, int64_t *offsets, int32_t *recv_from);
 
-/* ---- Point-cloud cleanup on the device (csrc/cloud_filter.hip): the three deterministic
- * neighbour steps of the reference's cleanup tab (two filters, and DBSCAN with the largest-cluster
+/* ---- Point-cloud cleanup on the device (csrc/cloud_grid.hip, cloud_filter.hip,
+ * cloud_cluster.hip): the three deterministic neighbour steps of the reference's cleanup tab (two filters, and DBSCAN with the largest-cluster
  * pick: slg_dbscan, below), on a packed DEVICE cloud (xyz float64 [n][3]), so a reconstructed view
  * is cleaned without leaving HBM.
  *   slg_radius_outlier      <- ProcessingLogic.remove_radius_outlier (server/processing.py:430-448)
@@ -474,7 +474,7 @@ int32_t slg_dbscan(const double *xyz, int64_t n, double eps, int32_t min_points,
                    void *stream);
 
 /* ---- Voxel down-sample, normals, orientation and centroid on the device cloud
- * (csrc/cloud_filter.hip): the Open3D operations of the tail of merge_pro_360
+ * (csrc/cloud_normals.hip): the Open3D operations of the tail of merge_pro_360
  * (server/processing.py:605-628) and of the front of both meshing methods (:653-670, :804-837).
  * Open3D's published rules restated, fp64, no floating-point atomics: the same input gives the
  * same bits.  ws, where a function takes one, is slg_filter_ws_bytes(n, 0) bytes; asynchronous on

@@ -26,10 +26,11 @@ import sys
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
-# the compiled files; the headers beside them (internal.h, workspace.h, otsu.h, code_object.h)
-# enter the digest through their directory
+# the compiled files; the headers beside them (internal.h, workspace.h, otsu.h, code_object.h,
+# cloud_grid.h) enter the digest through their directory
 SRCS = [os.path.join(CSRC, n) for n in ("slgpu.hip", "ply.hip", "color_gray.hip", "png_device.hip",
-                                        "cloud_filter.hip", "code_object.cpp", "png_gray.cpp", "gather.cpp")]
+                                        "cloud_grid.hip", "cloud_filter.hip", "cloud_cluster.hip",
+                                        "cloud_normals.hip", "code_object.cpp", "png_gray.cpp", "gather.cpp")]
 SRC_SUFFIXES = (".hip", ".cpp", ".h")
 HDR = os.path.join(ROOT, "include", "slgpu.h")
 OUT = os.path.join(PKG, "libslgpu.so")

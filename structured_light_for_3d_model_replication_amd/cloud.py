@@ -1,4 +1,4 @@
-"""Point clouds on the device and their cleanup filters (``csrc/cloud_filter.hip``).
+"""Point clouds on the device and their cleanup filters (``csrc/cloud_*.hip``).
 
 ``PointCloud`` is a packed float64 ``xyz`` + uint8 BGR ``bgr`` pair in HBM; :func:`radius_outlier`,
 :func:`statistical_outlier` and :func:`largest_cluster` are the three deterministic neighbour
@@ -29,7 +29,7 @@ from . import _native as N
 from . import engine as E
 from . import ply as PLY
 
-MAX_NEIGHBORS = 64          # kMaxK of csrc/cloud_filter.hip
+MAX_NEIGHBORS = 64          # kMaxK of csrc/cloud_grid.h
 
 _HEADER_TAIL = PLY.header(0).decode().split("\n")[3:-1]      # the property lines + end_header
 
@@ -216,19 +216,25 @@ def far_count(device) -> int:
     return int(_WS[device][8:12].view(torch.int32).item())
 
 
+def _call(fn, xyz: torch.Tensor, k: int, head, outs, stream, what=None) -> None:
+    """What every wrapper of a workspace call shares: the device guard, the workspace,
+    ``fn(*head, ws, ws_bytes, *outs, stream)``, the error, and (with ``what``) the status word."""
+    with torch.cuda.device(xyz.device):
+        ws = _workspace(xyz.shape[0], k, xyz.device)
+        _raise(fn(*head, E._vp(ws), ws.numel(), *(E._vp(o) for o in outs), E._stream(stream)))
+        if what:
+            _check_status(ws, what)
+
+
 def radius_mask(xyz: torch.Tensor, nb_points: int, radius: float, stream=None):
     """``(keep uint8 [n], counts int32 [n])`` on the device: ``counts[i]`` = points with
     ``d2 < radius**2`` (``i`` included), ``keep = counts > nb_points``."""
     xyz = _check_xyz(xyz)
     n = xyz.shape[0]
-    with torch.cuda.device(xyz.device):
-        ws = _workspace(n, 0, xyz.device)
-        keep = torch.empty(n, dtype=torch.uint8, device=xyz.device)
-        counts = torch.empty(n, dtype=torch.int32, device=xyz.device)
-        rc = N.lib().slg_radius_outlier(E._vp(xyz), n, float(radius), int(nb_points), E._vp(ws), ws.numel(),
-                                        E._vp(keep), E._vp(counts), E._stream(stream))
-        _raise(rc)
-        _check_status(ws, "radius_outlier")
+    keep = torch.empty(n, dtype=torch.uint8, device=xyz.device)
+    counts = torch.empty(n, dtype=torch.int32, device=xyz.device)
+    _call(N.lib().slg_radius_outlier, xyz, 0, (E._vp(xyz), n, float(radius), int(nb_points)), (keep, counts), stream,
+          "radius_outlier")
     return keep, counts
 
 
@@ -236,15 +242,11 @@ def statistical_mask(xyz: torch.Tensor, nb_neighbors: int, std_ratio: float, str
     """``(keep uint8 [n], avg float64 [n], stats float64 [3] = mean, std, thr)`` on the device."""
     xyz = _check_xyz(xyz)
     n = xyz.shape[0]
-    with torch.cuda.device(xyz.device):
-        ws = _workspace(n, min(int(nb_neighbors), MAX_NEIGHBORS), xyz.device)
-        keep = torch.empty(n, dtype=torch.uint8, device=xyz.device)
-        avg = torch.empty(n, dtype=torch.float64, device=xyz.device)
-        stats = torch.empty(3, dtype=torch.float64, device=xyz.device)
-        rc = N.lib().slg_statistical_outlier(E._vp(xyz), n, int(nb_neighbors), float(std_ratio), E._vp(ws),
-                                             ws.numel(), E._vp(keep), E._vp(avg), E._vp(stats), E._stream(stream))
-        _raise(rc)
-        _check_status(ws, "statistical_outlier")
+    keep = torch.empty(n, dtype=torch.uint8, device=xyz.device)
+    avg = torch.empty(n, dtype=torch.float64, device=xyz.device)
+    stats = torch.empty(3, dtype=torch.float64, device=xyz.device)
+    _call(N.lib().slg_statistical_outlier, xyz, min(int(nb_neighbors), MAX_NEIGHBORS),
+          (E._vp(xyz), n, int(nb_neighbors), float(std_ratio)), (keep, avg, stats), stream, "statistical_outlier")
     return keep, avg, stats
 
 
@@ -255,15 +257,10 @@ def dbscan_labels(xyz: torch.Tensor, eps: float, min_points: int, stream=None):
     ``info = (n_clusters, largest_label, largest_count, n_noise)``."""
     xyz = _check_xyz(xyz)
     n = xyz.shape[0]
-    with torch.cuda.device(xyz.device):
-        ws = _workspace(n, 0, xyz.device)
-        labels = torch.empty(n, dtype=torch.int32, device=xyz.device)
-        keep = torch.empty(n, dtype=torch.uint8, device=xyz.device)
-        info = torch.empty(4, dtype=torch.int32, device=xyz.device)
-        rc = N.lib().slg_dbscan(E._vp(xyz), n, float(eps), int(min_points), E._vp(ws), ws.numel(), E._vp(labels),
-                                E._vp(keep), E._vp(info), E._stream(stream))
-        _raise(rc)
-        _check_status(ws, "dbscan")
+    labels = torch.empty(n, dtype=torch.int32, device=xyz.device)
+    keep = torch.empty(n, dtype=torch.uint8, device=xyz.device)
+    info = torch.empty(4, dtype=torch.int32, device=xyz.device)
+    _call(N.lib().slg_dbscan, xyz, 0, (E._vp(xyz), n, float(eps), int(min_points)), (labels, keep, info), stream, "dbscan")
     return labels, keep, info
 
 
@@ -340,18 +337,14 @@ def voxel_down_sample(pc, voxel_size: float, return_index: bool = False, stream=
         raise ValueError("Point cloud is empty.")
     xyz = _check_xyz(pc.xyz)
     n, dev = xyz.shape[0], xyz.device
-    with torch.cuda.device(dev):
-        ws = _workspace(n, 0, dev)
-        oxyz = torch.empty((n, 3), dtype=torch.float64, device=dev)
-        obgr = torch.empty((n, 3), dtype=torch.uint8, device=dev)
-        first = torch.empty(n, dtype=torch.int64, device=dev)
-        count = torch.empty(n, dtype=torch.int32, device=dev)
-        m = torch.zeros(1, dtype=torch.int64, device=dev)
-        _raise(N.lib().slg_voxel_downsample(E._vp(xyz), E._vp(pc.bgr), n, float(voxel_size), E._vp(ws), ws.numel(),
-                                            E._vp(oxyz), E._vp(obgr), E._vp(first), E._vp(count), E._vp(m),
-                                            E._stream(stream)))
-        _check_status(ws, "voxel_down_sample")
-        m = int(m.item())
+    oxyz = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    obgr = torch.empty((n, 3), dtype=torch.uint8, device=dev)
+    first = torch.empty(n, dtype=torch.int64, device=dev)
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    m = torch.zeros(1, dtype=torch.int64, device=dev)
+    _call(N.lib().slg_voxel_downsample, xyz, 0, (E._vp(xyz), E._vp(pc.bgr), n, float(voxel_size)),
+          (oxyz, obgr, first, count, m), stream, "voxel_down_sample")
+    m = int(m.item())
     out = PointCloud(oxyz[:m], obgr[:m])
     return (out, first[:m], count[:m]) if return_index else out
 
@@ -371,14 +364,11 @@ def normal_covariances(xyz: torch.Tensor, radius: float, max_nn: int, stream=Non
     the device: the hybrid search's neighbour count, their covariance and the normal."""
     xyz = _check_xyz(xyz)
     n, dev = xyz.shape[0], xyz.device
-    with torch.cuda.device(dev):
-        ws = _workspace(n, 0, dev)
-        nrm = torch.empty((n, 3), dtype=torch.float64, device=dev)
-        cov = torch.empty((n, 6), dtype=torch.float64, device=dev)
-        m = torch.empty(n, dtype=torch.int32, device=dev)
-        _raise(N.lib().slg_estimate_normals(E._vp(xyz), n, float(radius), int(max_nn), E._vp(ws), ws.numel(),
-                                            E._vp(nrm), E._vp(cov), E._vp(m), E._stream(stream)))
-        _check_status(ws, "estimate_normals")
+    nrm = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    cov = torch.empty((n, 6), dtype=torch.float64, device=dev)
+    m = torch.empty(n, dtype=torch.int32, device=dev)
+    _call(N.lib().slg_estimate_normals, xyz, 0, (E._vp(xyz), n, float(radius), int(max_nn)), (nrm, cov, m), stream,
+          "estimate_normals")
     return cov, m, nrm
 
 
@@ -399,10 +389,8 @@ def centroid(pc, stream=None) -> torch.Tensor:
         raise ValueError("Point cloud is empty.")
     xyz = _check_xyz(pc.xyz)
     n, dev = xyz.shape[0], xyz.device
-    with torch.cuda.device(dev):
-        ws = _workspace(n, 0, dev)
-        out = torch.empty(3, dtype=torch.float64, device=dev)
-        _raise(N.lib().slg_cloud_centroid(E._vp(xyz), n, E._vp(ws), ws.numel(), E._vp(out), E._stream(stream)))
+    out = torch.empty(3, dtype=torch.float64, device=dev)
+    _call(N.lib().slg_cloud_centroid, xyz, 0, (E._vp(xyz), n), (out,), stream)
     return out
 
 

@@ -1,0 +1,384 @@
+// cloud_grid.h -- what the device cloud steps share (included, never compiled alone): the
+// workspace header, the sparse uniform grid's device helpers, the two neighbour walks, the top-k
+// lists, and the host functions of cloud_grid.hip.  Users: cloud_filter.hip (radius count,
+// statistical filter), cloud_cluster.hip (DBSCAN), cloud_normals.hip (voxel down-sample, normals).
+//
+// The grid: bbox (fixed-order reduction) -> integer cell coordinates floor((p - min) / cell)
+// packed into a 63-bit key (21 bits per axis, x lowest) -> stable radix sort of (key, index) ->
+// points gathered in sorted order -> table of unique keys + start offsets (binary search).  x is
+// the lowest key field, so the cells x0..x1 of one (y, z) row are one contiguous range of the
+// sorted cloud: a 3x3x3 neighbourhood is 9 ranges.  No dense cell array exists, so far outliers
+// (row_mode 2 clouds) cost nothing.
+//
+// Everything is separate launches on the caller's stream; no workgroup waits for another and
+// nothing synchronises with the host.  Conditions only the device can see (a non-finite
+// coordinate, an axis of 2^21 cells or more) set a status word at the front of the workspace;
+// every later kernel of the call reads it and returns, so a bad input ends in the flag.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "internal.h"
+
+namespace slgcloud {
+
+constexpr int kCellBits = 21;
+constexpr int64_t kCellMax = (1ll << kCellBits) - 1;
+constexpr int kMaxK = 64;
+constexpr int kTile = 1024;        // candidate points staged in LDS per tile (24 KB)
+constexpr int kChunk = 2048;       // points per workgroup in the fixed-order reductions
+constexpr int kMaxRing = 6;        // Chebyshev rings the kNN walk takes before the whole-cloud kernel
+constexpr double kInf = __builtin_huge_val();
+constexpr uint32_t kNone = 0xFFFFFFFFu;      // no index: not a core point, no root, an empty list head
+constexpr int64_t kMaxPoints = 1ll << 30;    // 32-bit sorted indices and offsets
+
+// ---------------------------------------------------------------- the shared rules
+// Squared distance: the same expression, in the same order, as tests/cloud_ref.py:d2.
+__device__ inline double d2_rule(double dx, double dy, double dz) { return (dx * dx + dy * dy) + dz * dz; }
+// A neighbour counts when d2 < radius^2 (strict); the point itself counts.
+__device__ inline bool radius_neighbour_rule(double d2, double r2) { return d2 < r2; }
+
+// ---------------------------------------------------------------- workspace
+struct Hdr {            // 256 bytes at the front of the workspace
+  int32_t status;       // SLG_FILTER_BAD_* bits
+  int32_t n_unique;
+  int32_t n_far;
+  int32_t pad;
+  double mn[3], mx[3];
+  double cell;
+  double slack;         // absolute rounding allowance on a face distance
+  int32_t cmax[3];
+  int32_t pad2;
+  double mean, std, thr;
+  int32_t n_clusters;   // slg_dbscan
+  int32_t n_noise;
+  unsigned long long best;   // (member count << 32) | ~label, by atomicMax: the lowest label wins a tie
+};
+static_assert(sizeof(Hdr) <= 256, "header");
+static_assert(offsetof(Hdr, status) == 0, "cloud.py reads the status word at byte 0");
+static_assert(offsetof(Hdr, n_far) == 8, "cloud.py reads n_far at byte 8 (far_count)");
+
+struct Ws {             // the regions of make_layout (cloud_grid.hip), bound to a caller's workspace
+  Hdr* hdr;
+  uint64_t *keys, *keys_s, *ukeys;
+  uint32_t *idx, *idx_s, *pos, *ustart, *far;
+  double *sxyz, *part, *avg;
+  void* temp;
+  size_t temp_bytes;
+};
+
+// Scratch of slg_dbscan and slg_voxel_downsample in regions their grid leaves idle (cloud_grid.hip).
+struct DbscanScratch {
+  int32_t* cnt;
+  uint32_t *scidx, *parent, *root, *sroot;
+  int32_t* sizes;
+  uint8_t* keep;
+  uint32_t* flags;
+};
+struct VoxelScratch { uint32_t *head, *place; };
+
+inline int grid_of(int64_t n, int per) { return (int)((n + per - 1) / per); }
+
+// ---------------------------------------------------------------- host side (cloud_grid.hip)
+// The point cap and the workspace binding every entry point starts with.
+int begin_call(const char* who, int64_t n, void* ws, int64_t ws_bytes, Ws* w);
+DbscanScratch dbscan_scratch(const Ws& w, int64_t n);
+VoxelScratch voxel_scratch(const Ws& w, int64_t n);
+// Clears the header, folds the box and fixes the cell (bbox_final_kernel says how).
+int bbox(const double* xyz, int64_t n, const Ws& w, double cell, int k, hipStream_t st);
+// keys -> stable sort by (key, index) -> sorted points -> cell table, with the header's cell size.
+int build_grid(const double* xyz, int64_t n, const Ws& w, hipStream_t st);
+// The kNN grid: the box, the first guess of the cell and two occupancy refinements.
+int knn_grid(const double* xyz, int64_t n, const Ws& w, int k, hipStream_t st);
+// out = exclusive sum of in[0..n) through the workspace's rocPRIM scratch.
+int scan_u32(const char* who, const Ws& w, const uint32_t* in, uint32_t* out, int64_t n, hipStream_t st);
+// Launches the radius count on a built grid (cloud_filter.hip); slg_dbscan starts from it too.
+void radius_count(const Ws& w, int64_t n, double r2, int32_t nb, uint8_t* keep, int32_t* counts, hipStream_t st);
+
+// ---------------------------------------------------------------- grid helpers
+__device__ inline int64_t cell_coord(double p, double mn, double cell) {
+  const double c = floor((p - mn) / cell);
+  if (!(c > 0.0)) return 0;                 // also NaN
+  return c > (double)kCellMax ? kCellMax : (int64_t)c;
+}
+__device__ inline uint64_t pack_key(int64_t x, int64_t y, int64_t z) {
+  return ((uint64_t)z << (2 * kCellBits)) | ((uint64_t)y << kCellBits) | (uint64_t)x;
+}
+__device__ inline void unpack_key(uint64_t key, int64_t* c) {
+  c[0] = key & kCellMax;
+  c[1] = (key >> kCellBits) & kCellMax;
+  c[2] = (key >> (2 * kCellBits)) & kCellMax;
+}
+// First table entry with key >= k (nu when none).
+__device__ inline int lower_bound(const uint64_t* __restrict__ a, int nu, uint64_t k) {
+  int lo = 0, hi = nu;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (a[mid] < k) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+// Sorted-cloud range [s, e) of the cells x0..x1 of row (y, z).
+__device__ inline void row_range(const uint64_t* __restrict__ ukeys, const uint32_t* __restrict__ ustart, int nu,
+                                 int64_t x0, int64_t x1, int64_t y, int64_t z, uint32_t* s, uint32_t* e) {
+  const int u0 = lower_bound(ukeys, nu, pack_key(x0, y, z));
+  const int u1 = lower_bound(ukeys, nu, pack_key(x1, y, z) + 1);
+  *s = ustart[u0];                           // ustart[nu] = n
+  *e = ustart[u1];
+}
+// The 9 row ranges of the 3x3x3 block around cell `key` (threads 0..8).
+__device__ inline void block_ranges(const Hdr* hdr, const uint64_t* __restrict__ ukeys,
+                                    const uint32_t* __restrict__ ustart, int nu, uint64_t key, uint32_t (*rng)[2]) {
+  const int t = threadIdx.x;
+  if (t >= 9) return;
+  int64_t c[3];
+  unpack_key(key, c);
+  const int64_t y = c[1] + (t % 3) - 1, z = c[2] + (t / 3) - 1;
+  uint32_t s = 0, e = 0;
+  if (y >= 0 && y <= hdr->cmax[1] && z >= 0 && z <= hdr->cmax[2])
+    row_range(ukeys, ustart, nu, c[0] > 0 ? c[0] - 1 : 0, c[0] < hdr->cmax[0] ? c[0] + 1 : c[0], y, z, &s, &e);
+  rng[t][0] = s;
+  rng[t][1] = e;
+}
+
+// ---------------------------------------------------------------- fixed-order trees (256 threads)
+// Σ v over the workgroup as a binary tree in sm[256]; every thread gets the sum.
+__device__ inline double block_tree_sum(double v, double* sm) {
+  const int t = threadIdx.x;
+  sm[t] = v;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) sm[t] = sm[t] + sm[t + s];
+    __syncthreads();
+  }
+  return sm[0];
+}
+// min of lo[0..2] and max of hi[0..2] over the workgroup: the results are sm[a][0] and sm[3 + a][0].
+__device__ inline void block_tree_minmax(const double* lo, const double* hi, double (*sm)[256]) {
+  const int t = threadIdx.x;
+  for (int a = 0; a < 3; ++a) { sm[a][t] = lo[a]; sm[3 + a][t] = hi[a]; }
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s)
+      for (int a = 0; a < 3; ++a) {
+        sm[a][t] = fmin(sm[a][t], sm[a][t + s]);
+        sm[3 + a][t] = fmax(sm[3 + a][t], sm[3 + a][t + s]);
+      }
+    __syncthreads();
+  }
+}
+__device__ inline double wave_min(double v) {
+  for (int s = 32; s > 0; s >>= 1) v = fmin(v, __shfl_xor(v, s, 64));
+  return v;
+}
+
+// ---------------------------------------------------------------- the block walk
+// One workgroup per occupied cell (grid-stride): the 9 ranges of the cell's block into rng, then
+// batch(qb, qe) for the cell's points [qb, qe) 256 at a time; thread t's query is qb + t.
+template <class Batch>
+__device__ inline void cell_batches(const Hdr* hdr, const uint64_t* __restrict__ ukeys,
+                                    const uint32_t* __restrict__ ustart, uint32_t (*rng)[2], Batch batch) {
+  if (hdr->status) return;
+  const int nu = hdr->n_unique;
+  for (int u = blockIdx.x; u < nu; u += gridDim.x) {
+    const uint32_t qs = ustart[u], qe = ustart[u + 1];
+    __syncthreads();                         // the previous cell's ranges are no longer read
+    block_ranges(hdr, ukeys, ustart, nu, ukeys[u], rng);
+    __syncthreads();
+    for (uint32_t qb = qs; qb < qe; qb += 256) batch(qb, qe);
+  }
+}
+// One batch of queries (one per thread, at (px, py, pz)) against the 9 ranges.  The candidates are
+// staged through LDS in tiles of kTile points and read back as broadcasts (every lane the same
+// address), so the inner loop is fp64 VALU fed from LDS.  stage(w, j) stages whatever words the
+// kernel keeps beside the coordinates for tile slot w = sorted position j; cand(w, d2) sees every
+// candidate of the tile.  A wave whose `gate` is off (none of its lanes holds a query that needs
+// the walk) only stages and takes the barriers.  Every thread of the workgroup must call this.
+template <bool kUnroll4, class Stage, class Cand>
+__device__ inline void block_walk(const uint32_t (*rng)[2], const double* __restrict__ sxyz, double* tile, bool gate,
+                                  double px, double py, double pz, Stage stage, Cand cand) {
+  const int t = threadIdx.x;
+  for (int r = 0; r < 9; ++r) {
+    const uint32_t s = rng[r][0], e = rng[r][1];
+    for (uint32_t tb = s; tb < e; tb += kTile) {
+      const int m = (int)(e - tb < (uint32_t)kTile ? e - tb : (uint32_t)kTile);
+      __syncthreads();                       // the previous tile has been consumed
+      for (int w = t; w < 3 * m; w += 256) tile[w] = sxyz[3 * (size_t)tb + w];
+      for (int w = t; w < m; w += 256) stage(w, tb + w);
+      __syncthreads();
+      if (!gate) continue;
+      if constexpr (kUnroll4) {
+#pragma unroll 4
+        for (int j = 0; j < m; ++j) cand(j, d2_rule(tile[3 * j] - px, tile[3 * j + 1] - py, tile[3 * j + 2] - pz));
+      } else {
+        for (int j = 0; j < m; ++j) cand(j, d2_rule(tile[3 * j] - px, tile[3 * j + 1] - py, tile[3 * j + 2] - pz));
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------- top-k lists
+// Per-lane top-kk lists in LDS, lst[j * 64 + lane] (lanes on consecutive addresses): unsorted
+// while filling, with the largest entry tracked; once full, a smaller entry replaces the largest
+// and the list is rescanned for the new one.  TopK orders by d2 alone; TopKI keeps the original
+// index beside the distance (idx[j * 64 + lane] after the kk * 64 distances) and orders by
+// (d2, index).  offer(d, sidx, j) is what the walks call for the candidate at sorted position j.
+// Two types on purpose: the rescans differ (v > m from -1, against the pair order).
+struct TopK {
+  double* lst;      // this lane's column
+  int kk, cnt, maxpos;
+  double curmax;
+  __device__ inline void insert(double d) {
+    if (cnt < kk) {
+      lst[cnt * 64] = d;
+      if (d > curmax) { curmax = d; maxpos = cnt; }
+      ++cnt;
+    } else if (d < curmax) {
+      lst[maxpos * 64] = d;
+      double m = -1.0;
+      int mp = 0;
+      for (int j = 0; j < kk; ++j) {
+        const double v = lst[j * 64];
+        if (v > m) { m = v; mp = j; }
+      }
+      curmax = m;
+      maxpos = mp;
+    }
+  }
+  __device__ inline void offer(double d, const uint32_t* __restrict__, size_t) { insert(d); }
+  __device__ inline void sort() {            // ascending insertion sort of the cnt entries
+    for (int a = 1; a < cnt; ++a) {
+      const double v = lst[a * 64];
+      int b = a - 1;
+      while (b >= 0 && lst[b * 64] > v) { lst[(b + 1) * 64] = lst[b * 64]; --b; }
+      lst[(b + 1) * 64] = v;
+    }
+  }
+};
+
+__device__ inline bool pair_before_rule(double a, uint32_t ai, double b, uint32_t bi) {
+  return a < b || (a == b && ai < bi);
+}
+
+struct TopKI {
+  double* lst;
+  uint32_t* idx;
+  int kk, cnt, maxpos;
+  double curmax;
+  uint32_t maxidx;
+  // a candidate at distance d can only enter when the list is open or d is no larger than its largest
+  __device__ inline bool wants(double d) const { return cnt < kk || d <= curmax; }
+  __device__ inline void insert(double d, uint32_t i) {
+    if (cnt < kk) {
+      lst[cnt * 64] = d;
+      idx[cnt * 64] = i;
+      if (cnt == 0 || pair_before_rule(curmax, maxidx, d, i)) { curmax = d; maxidx = i; maxpos = cnt; }
+      ++cnt;
+    } else if (pair_before_rule(d, i, curmax, maxidx)) {
+      lst[maxpos * 64] = d;
+      idx[maxpos * 64] = i;
+      double m = lst[0];
+      uint32_t mi = idx[0];
+      int mp = 0;
+      for (int j = 1; j < kk; ++j) {
+        const double v = lst[j * 64];
+        if (v >= m) {
+          const uint32_t vi = idx[j * 64];
+          if (pair_before_rule(m, mi, v, vi)) { m = v; mi = vi; mp = j; }
+        }
+      }
+      curmax = m;
+      maxidx = mi;
+      maxpos = mp;
+    }
+  }
+  __device__ inline void offer(double d, const uint32_t* __restrict__ sidx, size_t j) {
+    if (wants(d)) insert(d, sidx[j]);
+  }
+  __device__ inline void sort() {            // ascending insertion sort by (d2, index)
+    for (int a = 1; a < cnt; ++a) {
+      const double v = lst[a * 64];
+      const uint32_t vi = idx[a * 64];
+      int b = a - 1;
+      while (b >= 0 && pair_before_rule(v, vi, lst[b * 64], idx[b * 64])) {
+        lst[(b + 1) * 64] = lst[b * 64];
+        idx[(b + 1) * 64] = idx[b * 64];
+        --b;
+      }
+      lst[(b + 1) * 64] = v;
+      idx[(b + 1) * 64] = vi;
+    }
+  }
+};
+
+// ---------------------------------------------------------------- the ring walk
+// Offers the sorted positions s, s + step, ... below e to the list; with kRadius only those with
+// d2 < r2.
+template <bool kRadius, class List>
+__device__ inline void scan_range(List& tk, const double* __restrict__ sxyz, const uint32_t* __restrict__ sidx,
+                                  uint32_t s, uint32_t e, uint32_t step, const double* p, double r2) {
+  for (uint32_t j = s; j < e; j += step) {
+    const double d = d2_rule(sxyz[3 * (size_t)j] - p[0], sxyz[3 * (size_t)j + 1] - p[1], sxyz[3 * (size_t)j + 2] - p[2]);
+    if (!kRadius || radius_neighbour_rule(d, r2)) tk.offer(d, sidx, j);
+  }
+}
+
+// The nearest neighbours of the point at sorted position q, one point per thread: cells in
+// Chebyshev rings around the point's cell until the list is full and its largest d2 is no larger
+// than the squared distance to the nearest face of the block searched (faces at or past the
+// cloud's box do not count: nothing lies beyond them).  The face distance gives up the header's
+// absolute slack and a relative 1e-12, so rounding in the cell coordinates cannot end the walk
+// early.  With kRadius a candidate enters only with d2 < r2, and the walk also ends once the
+// block searched covers the radius ball (r2 no larger than the squared face distance), so a point
+// with fewer than kk neighbours inside the radius stops as soon as nothing further out could
+// count.  False when the point is still open after kMaxRing rings: it goes to the caller's
+// whole-cloud kernel.
+template <bool kRadius, class List>
+__device__ inline bool ring_walk(const Hdr* hdr, const double* __restrict__ sxyz, const uint32_t* __restrict__ sidx,
+                                 const uint64_t* __restrict__ ukeys, const uint32_t* __restrict__ ustart, int64_t q,
+                                 double r2, List& tk) {
+  const int nu = hdr->n_unique;
+  const double h = hdr->cell;
+  const double p[3] = {sxyz[3 * q], sxyz[3 * q + 1], sxyz[3 * q + 2]};
+  int64_t c[3], cm[3];
+  for (int a = 0; a < 3; ++a) { c[a] = cell_coord(p[a], hdr->mn[a], h); cm[a] = hdr->cmax[a]; }
+  bool done = false;
+  for (int R = 0; R <= kMaxRing && !done; ++R) {
+    for (int dz = -R; dz <= R; ++dz) {
+      const int64_t z = c[2] + dz;
+      if (z < 0 || z > cm[2]) continue;
+      for (int dy = -R; dy <= R; ++dy) {
+        const int64_t y = c[1] + dy;
+        if (y < 0 || y > cm[1]) continue;
+        auto cells = [&](int64_t x0, int64_t x1) {
+          uint32_t s, e;
+          row_range(ukeys, ustart, nu, x0, x1, y, z, &s, &e);
+          scan_range<kRadius>(tk, sxyz, sidx, s, e, 1, p, r2);
+        };
+        if (abs(dy) == R || abs(dz) == R) {  // a whole row of the shell
+          cells(c[0] - R < 0 ? 0 : c[0] - R, c[0] + R > cm[0] ? cm[0] : c[0] + R);
+        } else {                             // the row's two end cells
+          if (c[0] - R >= 0) cells(c[0] - R, c[0] - R);
+          if (c[0] + R <= cm[0]) cells(c[0] + R, c[0] + R);
+        }
+      }
+    }
+    double bound = kInf;
+    for (int a = 0; a < 3; ++a) {
+      if (c[a] - R > 0) bound = fmin(bound, p[a] - (hdr->mn[a] + (double)(c[a] - R) * h));
+      if (c[a] + R < cm[a]) bound = fmin(bound, (hdr->mn[a] + (double)(c[a] + R + 1) * h) - p[a]);
+    }
+    if (bound == kInf) {
+      done = true;                           // the whole cloud has been searched
+    } else if (kRadius || tk.cnt == tk.kk) {
+      const double b = fmax(bound - hdr->slack, 0.0);
+      const double b2 = (b * b) * (1.0 - 1e-12);
+      done = (kRadius && r2 <= b2) || (tk.cnt == tk.kk && tk.curmax <= b2);
+    }
+  }
+  return done;
+}
+
+}  // namespace slgcloud

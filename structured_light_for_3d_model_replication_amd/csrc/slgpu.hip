@@ -8,7 +8,8 @@
 // Beside this file: workspace.h (the per-view workspace layout), otsu.h (histogram / Otsu /
 // percentile device code the kernels below share), internal.h (last-error entry, launch check),
 // code_object.cpp (which kernels the built library carries), ply.hip (PLY text), color_gray.hip
-// (colour ingest), png_device.hip, png_gray.cpp, cloud_filter.hip, gather.cpp.
+// (colour ingest), png_device.hip, png_gray.cpp, the device cloud steps (cloud_grid.h,
+// cloud_grid.hip, cloud_filter.hip, cloud_cluster.hip, cloud_normals.hip), gather.cpp.
 //
 // Kernels here
 //   stats_kernel      white/black histograms (+ max contrast) -> last-arriving workgroup turns

@@ -2,8 +2,8 @@
 
 Open3D's ``RemoveRadiusOutliers`` / ``RemoveStatisticalOutliers`` as published, restated; parity
 with an installed Open3D is unpinned.  Each rule is one function here, as it is one
-``__device__`` function in ``csrc/cloud_filter.hip``.  ``cKDTree`` only proposes candidates (a
-slightly larger radius, ``k + 8`` neighbours); every distance is then recomputed with :func:`d2`.
+``__device__`` function in ``csrc/cloud_grid.h`` or ``csrc/cloud_filter.hip``.  ``cKDTree`` only
+proposes candidates (a slightly larger radius, ``k + 8`` neighbours); every distance is then recomputed with :func:`d2`.
 """
 import math
 

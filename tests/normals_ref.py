@@ -1,5 +1,5 @@
 """NumPy restatement of the voxel down-sample, the normal estimation, the orientation and the
-centroid of ``csrc/cloud_filter.hip`` (test helper, like ``cloud_ref.py``).
+centroid of ``csrc/cloud_normals.hip`` (test helper, like ``cloud_ref.py``).
 
 Open3D's ``VoxelDownSample``, ``EstimateNormals`` (``KDTreeSearchParamHybrid``) and
 ``OrientNormalsTowardsCameraLocation`` as published, restated; parity with an installed Open3D is
@@ -14,7 +14,7 @@ import numpy as np
 from cloud_ref import d2
 
 CELL_LIMIT = 1 << 21
-JACOBI_SWEEPS = 5          # kJacobiSweeps of csrc/cloud_filter.hip
+JACOBI_SWEEPS = 5          # kJacobiSweeps of csrc/cloud_normals.hip
 
 
 # ------------------------------------------------------------------ voxel down-sample

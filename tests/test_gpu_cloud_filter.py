@@ -1,4 +1,5 @@
-"""Device cloud filters (csrc/cloud_filter.hip) against the NumPy restatement (cloud_ref.py).
+"""Device cloud filters (csrc/cloud_filter.hip on the grid of csrc/cloud_grid.hip) against the
+NumPy restatement (cloud_ref.py).
 
 Base inputs: the smoke view (192x128 camera, 25 degrees, 44 frames, decoded 11+10 with Otsu) as
 the oracle reconstructs it, row_mode 1 (12,532 points) and row_mode 2 (25,064 points)."""

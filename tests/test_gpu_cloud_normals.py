@@ -1,4 +1,4 @@
-"""Device normal estimation, orientation and centroid (csrc/cloud_filter.hip) against the NumPy
+"""Device normal estimation, orientation and centroid (csrc/cloud_normals.hip) against the NumPy
 restatement (normals_ref.py), and ProcessingLogic.estimate_oriented_normals.
 
 Base inputs: the two smoke-view clouds of test_gpu_cloud_filter.py (12,532 and 25,064 points,

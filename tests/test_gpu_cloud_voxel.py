@@ -1,4 +1,4 @@
-"""Device voxel down-sample (csrc/cloud_filter.hip) against the NumPy restatement
+"""Device voxel down-sample (csrc/cloud_normals.hip) against the NumPy restatement
 (normals_ref.py), and the merge tail built on it.
 
 Base inputs: the two smoke-view clouds of test_gpu_cloud_filter.py (12,532 and 25,064 points) at
