@@ -522,6 +522,63 @@ int32_t slg_orient_normals(const double *xyz, double *normals, int64_t n, const 
 int32_t slg_cloud_centroid(const double *xyz, int64_t n, void *ws, int64_t ws_bytes,
                            double *centroid_out, void *stream);
 
+/* ---- Point-to-plane ICP and rigid transform on the device cloud (csrc/cloud_icp.hip; DESIGN.md
+ * §12): the deterministic part of the loop body of merge_pro_360 (server/processing.py:549-603).
+ * Open3D's published rules restated, fp64, no floating-point atomics: the same input gives the
+ * same bits.  Asynchronous on `stream`, no host synchronisation: every iteration is enqueued at
+ * once, and a `done` word on the device ends the ones that are left.
+ *
+ *   slg_cloud_transform     <- PointCloud.transform(T)
+ * p'[a] = ((T[a][0]*x + T[a][1]*y) + T[a][2]*z) + T[a][3]; normals the same with the 3x3 block and
+ * no translation.  T is HOST float64 [16], row-major; its last row must be exactly 0 0 0 1 and
+ * every entry finite.  normals / normals_out may be NULL; the outputs may be the inputs.
+ *
+ *   slg_icp_point_to_plane  <- registration_icp(source, target, max_dist, init,
+ *                              TransformationEstimationPointToPlane(),
+ *                              ICPConvergenceCriteria(rel_fitness, rel_rmse, max_iteration))
+ * Evaluation at a transform T (the accumulated one, applied to the original source each time):
+ *   p' = T p as above;  corr[i] = the target point with the smallest (d2, target input index),
+ *   d2 = d2(target - p'), among those with d2 < max_dist * max_dist (strict), or -1;
+ *   n_corr = their number; err2 = sum of their d2; fitness = n_corr / n_source;
+ *   inlier_rmse = sqrt(err2 / n_corr), 0 when n_corr = 0.
+ * Step: per correspondence r = ((p' - t) . n_t) summed x, y, z and J = [p' x n_t, n_t]; the 21
+ *   upper-triangle entries of sum J J', the 6 of sum J r, n_corr and err2 are fixed trees over the
+ *   source input order; JTJ x = -JTr by LDL' without pivoting in a fixed operation order; a pivot
+ *   <= 0 or not finite, n_corr = 0 or tgt_normals = NULL make the update the identity; else
+ *   R = Rz(x[2]) Ry(x[1]) Rx(x[0]), t = x[3:6], T <- U T.
+ * Loop: evaluate at init_T; then up to max_iteration times step and evaluate, stopping after an
+ *   evaluation with |fitness - previous| < rel_fitness and |rmse - previous| < rel_rmse.
+ *   max_iteration = 0 is evaluate_registration.
+ * ws is DEVICE scratch of slg_icp_ws_bytes(n_source, n_target, max_iteration) bytes, 8-byte
+ * aligned; the status word at its front as for the filters (a NaN or infinite source or target
+ * coordinate sets SLG_FILTER_BAD_NONFINITE; the outputs are then unspecified), and the int32 at
+ * byte 8 counts the queries, over all evaluations, that left the grid walk for the whole-target
+ * kernel.  init_T is HOST float64 [16] like T above.  result_out is DEVICE float64
+ * [SLG_ICP_RESULT_LEN]: T (16), fitness, inlier_rmse, n_corr, iterations (updates made),
+ * converged (1 when the stop test ended the loop), 3 unused.  corr_out is DEVICE int32 [n_source]
+ * or NULL: the last evaluation's correspondences.  log_out is DEVICE float64
+ * [max_iteration + 1][SLG_ICP_LOG_STRIDE] or NULL, one record per evaluation (iterations + 1 are
+ * written): the T it was made at (16), n_corr, err2, fitness, rmse, the 21 + 6 sums, the x of the
+ * step that followed (6, zeros when none), SLG_ICP_LOG_* flags, 2 unused.
+ *
+ * SLG_ERR_INVALID for n <= 0, max_dist <= 0 or NaN, max_iteration < 0, a negative or NaN
+ * criterion, a NULL required pointer, a bad T or a workspace that is too small;
+ * SLG_ERR_UNSUPPORTED above 2^30 points or 1000 iterations. */
+#define SLG_ICP_RESULT_LEN 24
+#define SLG_ICP_LOG_STRIDE 56
+#define SLG_ICP_LOG_STOP 1       /* the stop test held at this evaluation */
+#define SLG_ICP_LOG_SOLVED 2     /* a step followed: x was applied */
+#define SLG_ICP_LOG_SINGULAR 4   /* a step followed with the identity (pivot, n_corr = 0, no normals) */
+#define SLG_ICP_LOG_LAST 8       /* max_iteration updates were made */
+int64_t slg_icp_ws_bytes(int64_t n_source, int64_t n_target, int32_t max_iteration);
+int32_t slg_icp_point_to_plane(const double *src_xyz, int64_t n_source, const double *tgt_xyz,
+                               const double *tgt_normals, int64_t n_target, double max_dist,
+                               const double *init_T, double rel_fitness, double rel_rmse,
+                               int32_t max_iteration, void *ws, int64_t ws_bytes, double *result_out,
+                               int32_t *corr_out, double *log_out, void *stream);
+int32_t slg_cloud_transform(const double *xyz, const double *normals, int64_t n, const double *T,
+                            double *xyz_out, double *normals_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

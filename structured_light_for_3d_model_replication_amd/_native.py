@@ -154,8 +154,14 @@ EXPORTS = {
     "slg_estimate_normals": (c_i32, [c_vp, c_i64, c_dbl, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "slg_orient_normals": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i32, c_vp]),
     "slg_cloud_centroid": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "slg_icp_ws_bytes": (c_i64, [c_i64, c_i64, c_i32]),
+    "slg_icp_point_to_plane": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_dbl, ctypes.POINTER(c_dbl), c_dbl, c_dbl,
+                                       c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "slg_cloud_transform": (c_i32, [c_vp, c_vp, c_i64, ctypes.POINTER(c_dbl), c_vp, c_vp, c_vp]),
 }
 FILTER_BAD_NONFINITE, FILTER_BAD_EXTENT = 1, 2
+ICP_RESULT_LEN, ICP_LOG_STRIDE = 24, 56          # SLG_ICP_RESULT_LEN, SLG_ICP_LOG_STRIDE
+ICP_LOG_STOP, ICP_LOG_SOLVED, ICP_LOG_SINGULAR, ICP_LOG_LAST = 1, 2, 4, 8
 GATHER_ID_BYTES = 128
 
 

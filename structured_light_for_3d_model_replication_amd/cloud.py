@@ -13,6 +13,10 @@ The same grid carries the Open3D steps of the merge tail and of the front of bot
 :func:`uniform_down_sample`, :func:`estimate_normals`, :func:`orient_normals_towards` and
 :func:`centroid`.
 
+The loop body of ``merge_pro_360`` (``:549-603``) has its deterministic part here as well:
+:func:`registration_icp` (point to plane), :func:`evaluate_registration`, :func:`transform` and
+:func:`concat`.  FPFH features and RANSAC stay with the reference.
+
 The PLY reader takes exactly the file ``ProcessingLogic._save_ply`` writes (``ply.header``): ASCII,
 ``x y z red green blue``, or the same with ``nx ny nz`` after ``z`` (a cloud with normals).
 Anything else raises ``ValueError`` saying what differs.
@@ -181,8 +185,10 @@ def as_point_cloud(obj) -> PointCloud:
 _WS: dict = {}
 
 
-def _workspace(n: int, k: int, device) -> torch.Tensor:
-    need = int(N.lib().slg_filter_ws_bytes(n, k))
+def _workspace(n: int, k: int, device, need=None) -> torch.Tensor:
+    """The device's workspace, grown to ``need`` bytes (``slg_filter_ws_bytes(n, k)`` when not
+    given; a negative size is the call's error code)."""
+    need = int(N.lib().slg_filter_ws_bytes(n, k)) if need is None else int(need)
     if need < 0:
         N.check(-need)
     ws = _WS.get(device)
@@ -212,7 +218,8 @@ def _check_status(ws: torch.Tensor, what: str) -> None:
 def far_count(device) -> int:
     """Points the last :func:`statistical_mask` or :func:`normal_covariances` on ``device`` sent
     to the whole-cloud kernel (the ring walk reached its cap): the int32 at byte 8 of the
-    workspace.  A test hook."""
+    workspace.  After :func:`registration_icp` or :func:`evaluate_registration`: the source points
+    sent to the whole-target kernel, summed over the evaluations.  A test hook."""
     return int(_WS[device][8:12].view(torch.int32).item())
 
 
@@ -416,3 +423,139 @@ def orient_normals_towards(pc, location, outward: bool = False, stream=None):
         _raise(N.lib().slg_orient_normals(E._vp(xyz), E._vp(nrm), n, E._vp(loc), int(bool(outward)),
                                           E._stream(stream)))
     return PointCloud(pc.xyz, pc.bgr, normals=nrm)
+
+
+# ----------------------------------------------------------------------------- registration / merge loop
+class RegistrationResult:
+    """What :func:`registration_icp` and :func:`evaluate_registration` return: ``transformation``
+    (4x4 NumPy array), ``fitness``, ``inlier_rmse``, ``iterations`` (updates made), ``converged``
+    (the stop test ended the loop), ``correspondence_set`` (device int64 ``[m, 2]``: source index,
+    target index, in source order) and ``log`` (NumPy ``[iterations + 1, ICP_LOG_STRIDE]``, one
+    record per evaluation as ``include/slgpu.h`` lays it out, or ``None``)."""
+
+    def __init__(self, transformation, fitness, inlier_rmse, iterations, converged, correspondence_set, log):
+        self.transformation = transformation
+        self.fitness = fitness
+        self.inlier_rmse = inlier_rmse
+        self.iterations = iterations
+        self.converged = converged
+        self.correspondence_set = correspondence_set
+        self.log = log
+
+    def __repr__(self):
+        return (f"RegistrationResult(fitness={self.fitness:.6f}, inlier_rmse={self.inlier_rmse:.6g}, "
+                f"correspondences={len(self.correspondence_set)}, iterations={self.iterations}, "
+                f"converged={self.converged})")
+
+
+def _matrix4(T, what: str) -> np.ndarray:
+    """A copy of ``T`` as a C-ordered float64 4x4 whose last row is exactly ``0 0 0 1``
+    (``None``: the identity)."""
+    if T is None:
+        return np.eye(4)
+    if isinstance(T, torch.Tensor):
+        T = T.detach().cpu().numpy()
+    T = np.array(T, dtype=np.float64, order="C")
+    if T.shape != (4, 4):
+        raise ValueError(f"{what}: the transformation must be a 4x4 matrix, got shape {T.shape}")
+    if not np.isfinite(T).all() or not np.array_equal(T[3], [0.0, 0.0, 0.0, 1.0]):
+        raise ValueError(f"{what}: the transformation needs finite entries and a last row of 0 0 0 1")
+    return T
+
+
+def _dbl16(T: np.ndarray):
+    return T.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+
+def _register(what, source, target, max_correspondence_distance, init, relative_fitness, relative_rmse,
+              max_iteration, return_log, need_normals, stream) -> RegistrationResult:
+    source, target = as_point_cloud(source), as_point_cloud(target)
+    if not (source.has_points() and target.has_points()):
+        raise ValueError("Point cloud is empty.")
+    if need_normals and not target.has_normals():
+        raise ValueError(f"{what}: point-to-plane ICP needs target normals (estimate_normals)")
+    d, rf, rr, it = float(max_correspondence_distance), float(relative_fitness), float(relative_rmse), int(max_iteration)
+    if not d > 0.0:
+        raise ValueError(f"{what}: max_correspondence_distance must be > 0")
+    if not (rf >= 0.0 and rr >= 0.0):
+        raise ValueError(f"{what}: relative_fitness and relative_rmse must be >= 0")
+    if it < 0:
+        raise ValueError(f"{what}: max_iteration must be >= 0")
+    T0 = _matrix4(init, what)
+    src, tgt = _check_xyz(source.xyz), _check_xyz(target.xyz)
+    dev = src.device
+    if tgt.device != dev:
+        raise ValueError(f"{what}: source and target live on different devices")
+    nrm = target.normals.contiguous() if target.has_normals() else None
+    ns, nt = src.shape[0], tgt.shape[0]
+    L = N.lib()
+    with torch.cuda.device(dev):
+        ws = _workspace(0, 0, dev, need=L.slg_icp_ws_bytes(ns, nt, it))
+        out = torch.zeros(N.ICP_RESULT_LEN + (it + 1) * N.ICP_LOG_STRIDE, dtype=torch.float64, device=dev)
+        corr = torch.empty(ns, dtype=torch.int32, device=dev)
+        _raise(L.slg_icp_point_to_plane(E._vp(src), ns, E._vp(tgt), E._vp(nrm) if nrm is not None else None, nt, d,
+                                        _dbl16(T0), rf, rr, it, E._vp(ws), ws.numel(), E._vp(out),
+                                        E._vp(corr), E._vp(out[N.ICP_RESULT_LEN:]), E._stream(stream)))
+        _check_status(ws, what)
+        host = out.cpu().numpy()                             # the one read-back: result and log
+    res = host[:N.ICP_RESULT_LEN]
+    iterations = int(res[19])
+    log = host[N.ICP_RESULT_LEN:].reshape(it + 1, N.ICP_LOG_STRIDE)[:iterations + 1].copy() if return_log else None
+    si = torch.nonzero(corr >= 0).reshape(-1)
+    pairs = torch.stack([si, corr[si].to(torch.int64)], 1)
+    return RegistrationResult(res[:16].reshape(4, 4).copy(), float(res[16]), float(res[17]), iterations,
+                              bool(res[20]), pairs, log)
+
+
+def registration_icp(source, target, max_correspondence_distance, init=None, relative_fitness=1e-6,
+                     relative_rmse=1e-6, max_iteration=30, return_log=False, stream=None) -> RegistrationResult:
+    """Open3D ``registration_icp(source, target, max_correspondence_distance, init,
+    TransformationEstimationPointToPlane(), ICPConvergenceCriteria(relative_fitness, relative_rmse,
+    max_iteration))`` on the device (``csrc/cloud_icp.hip``; rules: DESIGN.md §12).  Every
+    iteration is enqueued at once and the result is read back once.  ``target`` needs normals
+    (``ValueError`` otherwise); ``init``: a 4x4 with a last row of ``0 0 0 1`` (default: the
+    identity)."""
+    return _register("registration_icp", source, target, max_correspondence_distance, init, relative_fitness,
+                     relative_rmse, max_iteration, return_log, True, stream)
+
+
+def evaluate_registration(source, target, max_correspondence_distance, transformation=None,
+                          stream=None) -> RegistrationResult:
+    """Open3D ``evaluate_registration``: fitness, inlier rmse and correspondences at
+    ``transformation``, with no update (``registration_icp`` with ``max_iteration=0``; the target
+    needs no normals)."""
+    return _register("evaluate_registration", source, target, max_correspondence_distance, transformation, 0.0, 0.0,
+                     0, False, False, stream)
+
+
+def transform(pc, T, stream=None) -> PointCloud:
+    """Open3D ``PointCloud.transform`` into a new cloud: ``p' = ((T[a][0] x + T[a][1] y) + T[a][2] z)
+    + T[a][3]``; normals, when present, by the 3x3 block; colours are kept (shared)."""
+    pc = as_point_cloud(pc)
+    M = _matrix4(T, "transform")
+    if not pc.has_points():
+        return pc
+    xyz = _check_xyz(pc.xyz)
+    n = xyz.shape[0]
+    oxyz = torch.empty_like(xyz)
+    nrm = pc.normals.contiguous() if pc.has_normals() else None
+    onrm = torch.empty_like(nrm) if nrm is not None else None
+    with torch.cuda.device(xyz.device):
+        _raise(N.lib().slg_cloud_transform(E._vp(xyz), E._vp(nrm) if nrm is not None else None, n, _dbl16(M),
+                                           E._vp(oxyz), E._vp(onrm) if onrm is not None else None, E._stream(stream)))
+    return PointCloud(oxyz, pc.bgr, normals=onrm)
+
+
+def concat(a, b) -> PointCloud:
+    """Open3D ``a += b`` into a new cloud: ``a``'s points, then ``b``'s (two device copies per
+    array); normals are kept only when both clouds have them."""
+    a, b = as_point_cloud(a), as_point_cloud(b)
+    if not b.has_points():
+        return a
+    if not a.has_points():
+        return b
+    if a.xyz.device != b.xyz.device:
+        raise ValueError("concat: the clouds live on different devices")
+    both = a.has_normals() and b.has_normals()
+    return PointCloud(torch.cat([a.xyz, b.xyz]), torch.cat([a.bgr, b.bgr]),
+                      normals=torch.cat([a.normals, b.normals]) if both else None)

@@ -1,7 +1,8 @@
 // cloud_grid.h -- what the device cloud steps share (included, never compiled alone): the
 // workspace header, the sparse uniform grid's device helpers, the two neighbour walks, the top-k
 // lists, and the host functions of cloud_grid.hip.  Users: cloud_filter.hip (radius count,
-// statistical filter), cloud_cluster.hip (DBSCAN), cloud_normals.hip (voxel down-sample, normals).
+// statistical filter), cloud_cluster.hip (DBSCAN), cloud_normals.hip (voxel down-sample, normals),
+// cloud_icp.hip (point-to-plane ICP's correspondence search).
 //
 // The grid: bbox (fixed-order reduction) -> integer cell coordinates floor((p - min) / cell)
 // packed into a 63-bit key (21 bits per axis, x lowest) -> stable radix sort of (key, index) ->
@@ -325,8 +326,8 @@ __device__ inline void scan_range(List& tk, const double* __restrict__ sxyz, con
   }
 }
 
-// The nearest neighbours of the point at sorted position q, one point per thread: cells in
-// Chebyshev rings around the point's cell until the list is full and its largest d2 is no larger
+// The nearest neighbours of the query p, one query per thread: cells in
+// Chebyshev rings around the query's cell until the list is full and its largest d2 is no larger
 // than the squared distance to the nearest face of the block searched (faces at or past the
 // cloud's box do not count: nothing lies beyond them).  The face distance gives up the header's
 // absolute slack and a relative 1e-12, so rounding in the cell coordinates cannot end the walk
@@ -335,15 +336,28 @@ __device__ inline void scan_range(List& tk, const double* __restrict__ sxyz, con
 // with fewer than kk neighbours inside the radius stops as soon as nothing further out could
 // count.  False when the point is still open after kMaxRing rings: it goes to the caller's
 // whole-cloud kernel.
-template <bool kRadius, class List>
-__device__ inline bool ring_walk(const Hdr* hdr, const double* __restrict__ sxyz, const uint32_t* __restrict__ sidx,
-                                 const uint64_t* __restrict__ ukeys, const uint32_t* __restrict__ ustart, int64_t q,
-                                 double r2, List& tk) {
+//
+// kOutside: the query need not be a point of the grid and may lie outside its box (the ICP's
+// transformed source points).  Its cell is then clamped into [0, cmax] per axis, and the face
+// bound stays a lower bound on the distance to everything not yet searched: on an axis where the
+// query lies beyond the box, the block's face on that side is at or past the box, so it is left
+// out as before (nothing lies beyond it), and the opposite face's plane lies between the query
+// and every point past it, so the query's distance to that plane, which is what the expression
+// below computes, is no larger than the distance to any such point.  The rounding of that
+// distance is relative to the query's coordinate; where that exceeds the header's slack (a query
+// far outside), the bound itself is of the coordinate's size and the relative 1e-12 covers it.
+template <bool kRadius, bool kOutside, class List>
+__device__ inline bool ring_walk_at(const Hdr* hdr, const double* __restrict__ sxyz, const uint32_t* __restrict__ sidx,
+                                    const uint64_t* __restrict__ ukeys, const uint32_t* __restrict__ ustart,
+                                    const double* p, double r2, List& tk) {
   const int nu = hdr->n_unique;
   const double h = hdr->cell;
-  const double p[3] = {sxyz[3 * q], sxyz[3 * q + 1], sxyz[3 * q + 2]};
   int64_t c[3], cm[3];
-  for (int a = 0; a < 3; ++a) { c[a] = cell_coord(p[a], hdr->mn[a], h); cm[a] = hdr->cmax[a]; }
+  for (int a = 0; a < 3; ++a) {
+    c[a] = cell_coord(p[a], hdr->mn[a], h);
+    cm[a] = hdr->cmax[a];
+    if (kOutside && c[a] > cm[a]) c[a] = cm[a];
+  }
   bool done = false;
   for (int R = 0; R <= kMaxRing && !done; ++R) {
     for (int dz = -R; dz <= R; ++dz) {
@@ -379,6 +393,15 @@ __device__ inline bool ring_walk(const Hdr* hdr, const double* __restrict__ sxyz
     }
   }
   return done;
+}
+
+// The walk for the grid's own point at sorted position q (it lies inside the box).
+template <bool kRadius, class List>
+__device__ inline bool ring_walk(const Hdr* hdr, const double* __restrict__ sxyz, const uint32_t* __restrict__ sidx,
+                                 const uint64_t* __restrict__ ukeys, const uint32_t* __restrict__ ustart, int64_t q,
+                                 double r2, List& tk) {
+  const double p[3] = {sxyz[3 * q], sxyz[3 * q + 1], sxyz[3 * q + 2]};
+  return ring_walk_at<kRadius, false>(hdr, sxyz, sidx, ukeys, ustart, p, r2, tk);
 }
 
 }  // namespace slgcloud

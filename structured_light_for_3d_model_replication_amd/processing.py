@@ -9,8 +9,10 @@ deterministic neighbour steps, which run on the device (``cloud.py``): ``remove_
 ``merge_pro_360`` (:605-628: voxel down-sample, uniform sample, outlier removal, normals) as
 ``merge_postprocess``, and the normal estimation and radial orientation that open
 ``reconstruct_stl`` and ``mesh_360`` (:653-670, :804-837) as ``estimate_oriented_normals``.
-Registration (FPFH, RANSAC, ICP), tangent-plane orientation, Poisson, ball pivoting and RANSAC
-plane removal are out of scope.
+``merge_pro_360`` itself (:489-629) runs on the device for scans whose initial poses are given:
+point-to-plane ICP, ``transform`` and ``+=``.  FPFH features, RANSAC global
+registration, tangent-plane orientation, Poisson, ball pivoting and RANSAC plane removal are out
+of scope.
 """
 from __future__ import annotations
 
@@ -237,6 +239,24 @@ def _is_frame0(texture, stack) -> bool:
     return t.shape[:2] == f0.shape and all(np.array_equal(t[..., c], f0) for c in range(3))
 
 
+def extract_degree(filepath) -> int:
+    """Sort key of ``merge_pro_360``'s files (``server/processing.py:499-517``): the integer of the
+    first ``_``-separated part of the file name that contains ``deg`` (``doraemon_30deg_scan.ply``
+    -> 30); without such a part the last number in the name; 0 when neither parses."""
+    import re
+    filename = os.path.basename(filepath)
+    try:
+        for part in filename.split('_'):
+            if 'deg' in part:
+                return int(part.replace('deg', ''))
+        numbers = re.findall(r'\d+', filename)
+        if numbers:
+            return int(numbers[-1])
+    except ValueError:
+        pass
+    return 0
+
+
 class ProcessingLogic:
     """Reconstruction half of the reference's ``ProcessingLogic`` (processing.py:12-334)."""
 
@@ -457,6 +477,84 @@ class ProcessingLogic:
             pcd_final.save(output_path)
             print(f"[Merge 360] Saved merged cloud to {output_path}")
         return pcd_final if return_obj else None
+
+    # --- 360-degree merge (device; cloud.py) ---
+    @staticmethod
+    def preprocess_point_cloud(pcd, voxel_size):
+        """Steps 1-2 of the reference's ``preprocess_point_cloud`` (``server/processing.py:451-468``)
+        on the device: voxel down-sample at ``voxel_size``, then normals with
+        ``radius = voxel_size * 2`` and ``max_nn = 30``.  Returns ``(pcd_down, None)``: there is no
+        FPFH here (step 3 feeds only the RANSAC this port leaves out), so ``None`` stands in its
+        place."""
+        from . import cloud as CL
+        pcd_down = CL.voxel_down_sample(pcd, voxel_size)
+        pcd_down = CL.estimate_normals(pcd_down, voxel_size * 2, 30)
+        return pcd_down, None
+
+    @staticmethod
+    def merge_pro_360(input_folder, output_path, voxel_size=0.02, icp_dist_ratio=1.5, outlier_nb=20, outlier_std=2.0,
+                      sample_before=1, sample_after=1, final_voxel=0.5, step_callback=None, init_transforms=None):
+        """Sequential merge of a folder of per-view PLY files (``server/processing.py:489-629``)
+        on the device, for scans whose initial poses are known.
+
+        File discovery, the degree sort, the errors and the print lines are the reference's.  Per
+        step both clouds are pre-processed (:meth:`preprocess_point_cloud`), the initial transform
+        of scan ``i`` onto scan ``i - 1`` is taken from ``init_transforms`` in place of the
+        reference's FPFH + RANSAC guess (a sequence of 4x4 matrices, entry ``i - 1`` for step
+        ``i``, or a callable ``(i, source_down, target_down) -> 4x4``; ``None``: the identity, for
+        scans already posed), point-to-plane ICP runs on the device with ``voxel_size`` as the
+        correspondence distance, the transform is accumulated, and the full-resolution source is
+        transformed and appended.  ``icp_dist_ratio`` only scaled the RANSAC distance and is
+        unused.  ``step_callback(i, total_steps, accumulated_cloud)`` gets a ``cloud.PointCloud``.
+        The tail is :meth:`merge_postprocess`; ``output_path`` is ASCII PLY with normals."""
+        from . import cloud as CL
+        print(f"[Merge 360] Loading clouds from {input_folder}...")
+        ply_files = sorted(glob.glob(os.path.join(input_folder, "*.ply")), key=extract_degree)
+        print(f"[Merge 360] Sorted file order:")
+        for idx, f in enumerate(ply_files):
+            print(f"  [{idx}] {os.path.basename(f)}")
+        if len(ply_files) < 2:
+            raise ValueError("Need at least 2 .ply files to merge.")
+        pcds = []
+        for path in ply_files:
+            pcd = CL.PointCloud.from_file(path)
+            if not pcd.has_points():
+                raise ValueError(f"Loaded empty point cloud from: {path}")
+            if sample_before > 1:
+                pcd = CL.uniform_down_sample(pcd, int(sample_before))
+            pcds.append(pcd)
+            print(f"  Loaded: {os.path.basename(path)} ({len(pcd)} points)")
+        total_steps = len(pcds) - 1
+        print(f"[Merge 360] Loaded {len(pcds)} clouds. Running Sequential Registration ({total_steps} steps)...")
+        merged_cloud = pcds[0]
+        max_accum_T = np.identity(4)
+        for i in range(1, len(pcds)):
+            print(f"\n[Merge 360] === Step {i}/{total_steps}: Aligning Scan {i} -> Scan {i-1} ===")
+            source, target = pcds[i], pcds[i - 1]
+            source_down, _ = ProcessingLogic.preprocess_point_cloud(source, voxel_size)
+            target_down, _ = ProcessingLogic.preprocess_point_cloud(target, voxel_size)
+            print(f"  Preprocessed: source={len(source_down)} pts, target={len(target_down)} pts (voxel={voxel_size})")
+            if init_transforms is None:
+                init = np.identity(4)
+            elif callable(init_transforms):
+                init = init_transforms(i, source_down, target_down)
+            else:
+                init = init_transforms[i - 1]
+            print("  [RANSAC] skipped: initial transform given")
+            icp_result = CL.registration_icp(source_down, target_down, voxel_size, init)
+            print(f"  [ICP]    Fitness: {icp_result.fitness:.4f} | RMSE: {icp_result.inlier_rmse:.6f}")
+            if icp_result.fitness < 0.05:
+                print(f"  [WARNING] Step {i}: ICP fitness is very low ({icp_result.fitness:.4f})! "
+                      f"This step's alignment is likely incorrect and WILL corrupt all subsequent steps. "
+                      f"Consider adjusting parameters or checking if all PLY files are valid.")
+            max_accum_T = np.dot(max_accum_T, icp_result.transformation)
+            merged_cloud = CL.concat(merged_cloud, CL.transform(source, max_accum_T))
+            print(f"  [Merge 360] Step {i}/{total_steps} complete. Accumulated cloud: {len(merged_cloud)} points total.")
+            if step_callback is not None:
+                step_callback(i, total_steps, merged_cloud)      # concat made a new cloud: nothing to protect
+        print(f"\n[Merge 360] All {total_steps} steps complete. Running post-processing...")
+        ProcessingLogic.merge_postprocess(merged_cloud, output_path, voxel_size, outlier_nb, outlier_std, sample_after,
+                                          final_voxel)
 
     @staticmethod
     def estimate_oriented_normals(input_data, save_normals_path=None, normal_radius=0.1, normal_max_nn=30,

@@ -21,6 +21,14 @@ host side is tests/normals_ref.py, its neighbour lists proposed by cKDTree and r
 (d2, index); positions, colours, counts, ``m`` and ``cov`` are compared, not just timed.
 ``--skip-cluster`` leaves the cluster step out.
 
+``--icp DIST`` adds the point-to-plane ICP.  Target: the view's cloud with normals
+(radius ``2 * DIST``, max_nn 30: the merge loop's relation between the two).  Source: the same
+cloud moved by the inverse of a fixed small motion (a rotation about the centroid and a translation,
+together about ``0.5 * DIST`` on the points).  HIP events go around the whole registration at the
+reference's defaults (1e-6, 1e-6, 30), status and result read-back included; the host side is
+tests/icp_ref.py over cKDTree with ``workers`` threads, and iterations, convergence, the final
+correspondences and the transform are compared.  ``--icp-only`` leaves everything else out.
+
 Prints one JSON line.
 """
 from __future__ import annotations
@@ -50,6 +58,8 @@ def main():
     ap.add_argument("--normals", nargs=2, metavar=("RADIUS", "MAX_NN"),
                     help="also time the normal estimation at this radius and max_nn")
     ap.add_argument("--skip-cluster", action="store_true", help="leave the cluster step out")
+    ap.add_argument("--icp", type=float, metavar="DIST", help="also time the point-to-plane ICP at this distance")
+    ap.add_argument("--icp-only", action="store_true", help="with --icp: leave every other step out")
     args = ap.parse_args()
 
     import numpy as np
@@ -82,6 +92,40 @@ def main():
 
     res = {"tool": "cloud_filter_bench", "points": n, "row_mode": args.row_mode, "cam": [W, H],
            "steps": args.steps, "device": torch.cuda.get_device_name(0)}
+    if args.icp:
+        import icp_ref as IR
+        d = float(args.icp)
+        tgt = CL.estimate_normals(pc, 2 * d, 30)
+        P = pc.xyz.cpu().numpy()
+        reach = float(np.linalg.norm(P - P.mean(0), axis=1).max())
+        angles = np.degrees(0.3 * d / reach) * np.array([1.0, -1.5, 0.7]) / 1.5
+        T_true = IR.motion_about(P.mean(0), angles, d * np.array([0.2, -0.15, 0.1]))
+        src = CL.transform(CL.PointCloud(pc.xyz, pc.bgr), IR.inverse_rigid(T_true))
+        reg, ms = timed(lambda: CL.registration_icp(src, tgt, d))
+        _, ms_eval = timed(lambda: CL.evaluate_registration(src, tgt, d))
+        S = src.xyz.cpu().numpy()
+        res["icp"] = {"dist": d, "normal_radius": 2 * d, "source_points": len(src), "target_points": len(tgt),
+                      "device_ms": ms, "device_evaluate_only_ms": ms_eval, "iterations": reg.iterations,
+                      "converged": reg.converged, "fitness": reg.fitness, "inlier_rmse": reg.inlier_rmse,
+                      "whole_target_queries": CL.far_count(pc.xyz.device),
+                      "motion_error": IR.motion_error(reg.transformation, T_true, S)}
+        if not args.no_cpu:
+            nrm = tgt.normals.cpu().numpy()
+            t0 = time.perf_counter()
+            ref = IR.registration_icp(S, P, nrm, d, workers=args.workers)
+            cpu_ms = (time.perf_counter() - t0) * 1e3
+            at_dev = IR.evaluate(S, P, reg.transformation, d, workers=args.workers)["corr"]
+            i = np.flatnonzero(at_dev >= 0)
+            res["icp"].update({
+                "cpu_ms": cpu_ms, "cpu_what": f"tests/icp_ref.py, scipy cKDTree(workers={args.workers})",
+                "iterations_equal_cpu": bool(ref["iterations"] == reg.iterations and ref["converged"] == reg.converged),
+                "correspondences_equal_cpu": bool(np.array_equal(reg.correspondence_set.cpu().numpy(),
+                                                                 np.stack([i, at_dev[i].astype(np.int64)], 1))),
+                "max_transform_difference_cpu": float(np.abs(ref["T"] - reg.transformation).max()),
+                "speedup_vs_cpu": cpu_ms / (sum(ms) / args.steps)})
+        if args.icp_only:
+            print(json.dumps(res))
+            return
     (rad, rad_idx), ms = timed(lambda: CL.radius_outlier(pc, 100, 5.0, return_index=True))
     res["radius"] = {"nb_points": 100, "radius": 5.0, "kept": len(rad), "device_ms": ms}
     (_, counts), ms = timed(lambda: CL.radius_mask(pc.xyz, 100, 5.0))
