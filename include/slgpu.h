@@ -458,6 +458,7 @@ int32_t slg_gatherv_plan(int32_t n_ranks, int32_t rank, int32_t root, int64_t se
  * above 2^30 points. */
 #define SLG_FILTER_BAD_NONFINITE 1
 #define SLG_FILTER_BAD_EXTENT 2
+#define SLG_FILTER_BAD_INDEX 4      /* slg_ransac_batch: a correspondence names a point outside its cloud */
 int64_t slg_filter_ws_bytes(int64_t n, int32_t k);
 int32_t slg_radius_outlier(const double *xyz, int64_t n, double radius, int32_t nb_points, void *ws,
                            int64_t ws_bytes, uint8_t *keep_out, int32_t *counts_out, void *stream);
@@ -578,6 +579,83 @@ int32_t slg_icp_point_to_plane(const double *src_xyz, int64_t n_source, const do
                                int32_t *corr_out, double *log_out, void *stream);
 int32_t slg_cloud_transform(const double *xyz, const double *normals, int64_t n, const double *T,
                             double *xyz_out, double *normals_out, void *stream);
+
+/* ---- FPFH features, feature matching and seeded RANSAC global registration on the device cloud
+ * (csrc/cloud_feature.hip, csrc/cloud_ransac.hip): what merge_pro_360 needs to find
+ * a scan's initial pose itself (server/processing.py:451-486).  Open3D's published rules restated
+ * (places where the rule is ours are marked so in DESIGN.md), fp64, no floating-point atomics: the
+ * same input, and the same seed, give the same bits.  Asynchronous on `stream`; the status word at
+ * the front of ws as for the filters.
+ *
+ *   slg_fpfh                <- compute_fpfh_feature(pcd, KDTreeSearchParamHybrid(radius, max_nn))
+ * Neighbours of i: slg_estimate_normals' hybrid search (the first min(max_nn, n) of all points in
+ * (d2, input index) order, of those the ones with d2 < radius * radius), m of them, i included.
+ * SPFH of i: for every neighbour but i itself (left out by index), Open3D's pair feature of
+ * (p_i, n_i), (p_j, n_j) with the roles swapped when |a1| < |a2|; each of the three features adds
+ * 100 / (m - 1) to the bin floor(11 * (theta + pi) / (2 pi)), floor(11 * (alpha + 1) * 0.5),
+ * floor(11 * (phi + 1) * 0.5) (clamped to 0..10) of its third, in list order.  FPFH of i: over the
+ * same list, skipping d2 = 0, spfh[j] / d2 added to the feature and to its third's sum; each third
+ * scaled by 100 / sum where the sum is not zero; plus spfh[i].  m <= 1 gives a zero row.
+ * fpfh_out float64 [n][SLG_FPFH_DIM]; spfh_out (the same shape) and m_out int32 [n] may be NULL.
+ * 2 <= max_nn <= SLG_FPFH_MAX_NN.  ws: slg_fpfh_ws_bytes(n, max_nn) bytes; afterwards the int32 at
+ * byte 8 counts the points that left the grid walk for the whole-cloud kernel.
+ *
+ *   slg_feature_match       <- the correspondence search of registration_ransac_based_on_feature_matching
+ * nn_source[i] = the target row with the smallest (d2, target index), d2 = sum over j = 0..32 of
+ * (a_j - b_j)^2 left to right, by exact brute force.  With mutual_filter the pair (i, nn_source[i])
+ * is kept only when the reverse search from nn_source[i] returns i.  pairs_out int64 [n_source][2]
+ * gets the kept pairs in source order, *m_out (DEVICE int64) their number.  nn_source_out int32
+ * [n_source] and nn_target_out int32 [n_target] (written with mutual_filter only) may be NULL.
+ *
+ *   slg_ransac_prepare / slg_ransac_batch
+ * prepare builds the target's grid in ws once per registration.  batch runs the trials
+ * first_trial .. first_trial + batch - 1 on it: trial t draws three indices into `pairs`
+ * (((h >> 32) * n_pairs) >> 32 with h = mix(mix(seed + 0x9E3779B97F4A7C15) + 4 t + k), mix the
+ * finaliser of SplitMix64); the draws must be distinct and every pair of the three must satisfy
+ * ds2 >= dt2 * e^2 and dt2 >= ds2 * e^2 on the squared edge lengths; T is the rigid least-squares
+ * transform of the three pairs (Horn's quaternion, a proper rotation, last row 0 0 0 1); all three
+ * must satisfy d2(T s - t) <= max_dist^2.  Every trial that passes is evaluated as
+ * slg_icp_point_to_plane evaluates a transform (n_corr, err2, fitness, rmse against the whole
+ * target) and gets the number of pairs with d2(T s - t) < max_dist^2, up to max_eval trials per
+ * call: a batch in which more pass ends before the first one left out.  records_out float64
+ * [batch][SLG_RANSAC_RECORD_STRIDE] holds one record per evaluated trial in ascending trial order;
+ * n_eval_out (DEVICE int32 [2]) their number and the number of trials the call dealt with (batch,
+ * or fewer: the next call's first_trial is this call's plus that).  A record: trial, the three draws, T (16), n_corr, err2, fitness,
+ * rmse, inliers, 7 unused.  trials_out float64 [batch][SLG_RANSAC_TRIAL_STRIDE] or NULL: per trial
+ * the draws, SLG_RANSAC_EDGE_OK | SLG_RANSAC_DISTANCE_OK, and T (16; the identity when the edge
+ * checker failed).  corr_out int32 [corr_cap][n_source] or NULL: the correspondences (-1: none) of
+ * the first corr_cap records.  The choice among the records is sequential in the trial number and
+ * is the host's (cloud.py); `confidence` belongs to it and is only validated here.
+ *
+ * SLG_ERR_INVALID for n <= 0, a radius or distance that is not finite and > 0, max_nn < 2,
+ * edge_length or confidence outside [0, 1], a NULL required buffer (slg_fpfh needs normals) or a
+ * workspace that is too small; SLG_ERR_UNSUPPORTED above 2^30 points, max_nn > SLG_FPFH_MAX_NN,
+ * ransac_n != 3 or batch > SLG_RANSAC_MAX_BATCH. */
+#define SLG_FPFH_DIM 33
+#define SLG_FPFH_MAX_NN 128
+#define SLG_RANSAC_MAX_BATCH 16384
+#define SLG_RANSAC_TRIAL_STRIDE 20
+#define SLG_RANSAC_RECORD_STRIDE 32
+#define SLG_RANSAC_EDGE_OK 1
+#define SLG_RANSAC_DISTANCE_OK 2
+int64_t slg_fpfh_ws_bytes(int64_t n, int32_t max_nn);
+int32_t slg_fpfh(const double *xyz, const double *normals, int64_t n, double radius, int32_t max_nn,
+                 void *ws, int64_t ws_bytes, double *fpfh_out, double *spfh_out, int32_t *m_out,
+                 void *stream);
+int64_t slg_feature_match_ws_bytes(int64_t n_source, int64_t n_target);
+int32_t slg_feature_match(const double *source_feature, int64_t n_source, const double *target_feature,
+                          int64_t n_target, int32_t mutual_filter, void *ws, int64_t ws_bytes,
+                          int32_t *nn_source_out, int32_t *nn_target_out, int64_t *pairs_out,
+                          int64_t *m_out, void *stream);
+int64_t slg_ransac_ws_bytes(int64_t n_source, int64_t n_target, int32_t batch);
+int32_t slg_ransac_prepare(const double *tgt_xyz, int64_t n_target, void *ws, int64_t ws_bytes,
+                           void *stream);
+int32_t slg_ransac_batch(const double *src_xyz, int64_t n_source, const double *tgt_xyz,
+                         int64_t n_target, const int64_t *pairs, int64_t n_pairs, int32_t ransac_n,
+                         double edge_length, double max_dist, double confidence, int64_t seed,
+                         int64_t first_trial, int32_t batch, void *ws, int64_t ws_bytes, int32_t max_eval,
+                         double *records_out, int32_t *n_eval_out, double *trials_out,
+                         int32_t *corr_out, int32_t corr_cap, void *stream);
 
 #ifdef __cplusplus
 }

@@ -158,8 +158,19 @@ EXPORTS = {
     "slg_icp_point_to_plane": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_dbl, ctypes.POINTER(c_dbl), c_dbl, c_dbl,
                                        c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "slg_cloud_transform": (c_i32, [c_vp, c_vp, c_i64, ctypes.POINTER(c_dbl), c_vp, c_vp, c_vp]),
+    "slg_fpfh_ws_bytes": (c_i64, [c_i64, c_i32]),
+    "slg_fpfh": (c_i32, [c_vp, c_vp, c_i64, c_dbl, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "slg_feature_match_ws_bytes": (c_i64, [c_i64, c_i64]),
+    "slg_feature_match": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "slg_ransac_ws_bytes": (c_i64, [c_i64, c_i64, c_i32]),
+    "slg_ransac_prepare": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "slg_ransac_batch": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_dbl, c_dbl, c_dbl, c_i64, c_i64,
+                                 c_i32, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
 }
-FILTER_BAD_NONFINITE, FILTER_BAD_EXTENT = 1, 2
+FILTER_BAD_NONFINITE, FILTER_BAD_EXTENT, FILTER_BAD_INDEX = 1, 2, 4
+FPFH_DIM, FPFH_MAX_NN = 33, 128                  # SLG_FPFH_DIM, SLG_FPFH_MAX_NN
+RANSAC_MAX_BATCH, RANSAC_TRIAL_STRIDE, RANSAC_RECORD_STRIDE = 16384, 20, 32
+RANSAC_EDGE_OK, RANSAC_DISTANCE_OK = 1, 2
 ICP_RESULT_LEN, ICP_LOG_STRIDE = 24, 56          # SLG_ICP_RESULT_LEN, SLG_ICP_LOG_STRIDE
 ICP_LOG_STOP, ICP_LOG_SOLVED, ICP_LOG_SINGULAR, ICP_LOG_LAST = 1, 2, 4, 8
 GATHER_ID_BYTES = 128

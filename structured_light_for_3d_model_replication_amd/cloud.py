@@ -15,7 +15,10 @@ The same grid carries the Open3D steps of the merge tail and of the front of bot
 
 The loop body of ``merge_pro_360`` (``:549-603``) has its deterministic part here as well:
 :func:`registration_icp` (point to plane), :func:`evaluate_registration`, :func:`transform` and
-:func:`concat`.  FPFH features and RANSAC stay with the reference.
+:func:`concat`.  The initial pose the reference finds per pair is here too:
+:func:`compute_fpfh_feature`, :func:`correspondences_from_features` and the seeded
+:func:`registration_ransac_based_on_feature_matching` (``server/processing.py:451-486``;
+DESIGN.md §13).
 
 The PLY reader takes exactly the file ``ProcessingLogic._save_ply`` writes (``ply.header``): ASCII,
 ``x y z red green blue``, or the same with ``nx ny nz`` after ``z`` (a cloud with normals).
@@ -24,6 +27,7 @@ Anything else raises ``ValueError`` saying what differs.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -34,6 +38,8 @@ from . import engine as E
 from . import ply as PLY
 
 MAX_NEIGHBORS = 64          # kMaxK of csrc/cloud_grid.h
+RANSAC_BATCH = 4096         # trials per slg_ransac_batch: one read-back of the evaluated trials' records each
+RANSAC_MAX_EVAL = 64        # evaluations per batch: where more trials pass, the batch ends early (K shrinks fast there)
 
 _HEADER_TAIL = PLY.header(0).decode().split("\n")[3:-1]      # the property lines + end_header
 
@@ -213,6 +219,8 @@ def _check_status(ws: torch.Tensor, what: str) -> None:
         raise ValueError(f"{what}: the cloud holds a NaN or infinite coordinate")
     if status & N.FILTER_BAD_EXTENT:
         raise ValueError(f"{what}: the cloud spans 2^21 or more cells of the radius or voxel size on an axis")
+    if status & N.FILTER_BAD_INDEX:
+        raise ValueError(f"{what}: a correspondence names a point outside its cloud")
 
 
 def far_count(device) -> int:
@@ -431,7 +439,15 @@ class RegistrationResult:
     (4x4 NumPy array), ``fitness``, ``inlier_rmse``, ``iterations`` (updates made), ``converged``
     (the stop test ended the loop), ``correspondence_set`` (device int64 ``[m, 2]``: source index,
     target index, in source order) and ``log`` (NumPy ``[iterations + 1, ICP_LOG_STRIDE]``, one
-    record per evaluation as ``include/slgpu.h`` lays it out, or ``None``)."""
+    record per evaluation as ``include/slgpu.h`` lays it out, or ``None``).
+
+    From :func:`registration_ransac_based_on_feature_matching`: ``iterations`` is the final ``K``
+    (the trials the choice ran over), ``converged`` says whether ``K`` ended below
+    ``max_iteration``, ``log`` holds one record per evaluated trial below ``K``
+    (``[*, RANSAC_RECORD_STRIDE]``: trial, the three draws, T, n_corr, err2, fitness, rmse,
+    inliers), and ``trial`` is the winner's trial number (-1: none passed)."""
+
+    trial = None
 
     def __init__(self, transformation, fitness, inlier_rmse, iterations, converged, correspondence_set, log):
         self.transformation = transformation
@@ -559,3 +575,213 @@ def concat(a, b) -> PointCloud:
     both = a.has_normals() and b.has_normals()
     return PointCloud(torch.cat([a.xyz, b.xyz]), torch.cat([a.bgr, b.bgr]),
                       normals=torch.cat([a.normals, b.normals]) if both else None)
+
+
+# ----------------------------------------------------------------------------- global registration
+def _check_features(f, what: str) -> torch.Tensor:
+    if not (isinstance(f, torch.Tensor) and f.is_cuda and f.dtype == torch.float64 and f.ndim == 2
+            and f.shape[1] == N.FPFH_DIM):
+        raise ValueError(f"{what}: features are device float64 [n, {N.FPFH_DIM}] tensors")
+    if f.shape[0] == 0:
+        raise ValueError(f"{what}: a feature tensor is empty")
+    return f.contiguous()
+
+
+def fpfh_features(pc, radius: float, max_nn: int = 100, stream=None):
+    """``(fpfh float64 [n, 33], spfh float64 [n, 33], m int32 [n])`` on the device: the feature,
+    the simplified histogram it is built from, and the hybrid search's neighbour count (the point
+    included)."""
+    pc = as_point_cloud(pc)
+    if not pc.has_points():
+        raise ValueError("Point cloud is empty.")
+    if not pc.has_normals():
+        raise ValueError("compute_fpfh_feature: the cloud has no normals (estimate_normals)")
+    xyz = _check_xyz(pc.xyz)
+    n, dev = xyz.shape[0], xyz.device
+    fpfh = torch.empty((n, N.FPFH_DIM), dtype=torch.float64, device=dev)
+    spfh = torch.empty((n, N.FPFH_DIM), dtype=torch.float64, device=dev)
+    m = torch.empty(n, dtype=torch.int32, device=dev)
+    L = N.lib()
+    with torch.cuda.device(dev):
+        ws = _workspace(0, 0, dev, need=L.slg_fpfh_ws_bytes(n, int(max_nn)))
+        _raise(L.slg_fpfh(E._vp(xyz), E._vp(pc.normals.contiguous()), n, float(radius), int(max_nn), E._vp(ws), ws.numel(),
+                          E._vp(fpfh), E._vp(spfh), E._vp(m), E._stream(stream)))
+        _check_status(ws, "compute_fpfh_feature")
+    return fpfh, spfh, m
+
+
+def compute_fpfh_feature(pc, radius: float, max_nn: int = 100, stream=None) -> torch.Tensor:
+    """Open3D ``compute_fpfh_feature(pc, KDTreeSearchParamHybrid(radius, max_nn))`` on the device
+    (``csrc/cloud_feature.hip``; rules: DESIGN.md §13): float64 ``[n, 33]``, one row per point
+    (Open3D's ``Feature.data`` is the transpose).  ``2 <= max_nn <= 128``; the cloud needs normals
+    (``ValueError`` otherwise)."""
+    return fpfh_features(pc, radius, max_nn, stream)[0]
+
+
+def feature_nearest(source_feature: torch.Tensor, target_feature: torch.Tensor, mutual_filter: bool = False, stream=None):
+    """``(pairs int64 [m, 2], nn_source int32 [n_source], nn_target int32 [n_target] or None)`` on
+    the device: per source row the target row with the smallest (d2, index), the reverse search
+    (with ``mutual_filter`` only) and the kept pairs in source order."""
+    a = _check_features(source_feature, "correspondences_from_features")
+    b = _check_features(target_feature, "correspondences_from_features")
+    dev = a.device
+    if b.device != dev:
+        raise ValueError("correspondences_from_features: the features live on different devices")
+    ns, nt = a.shape[0], b.shape[0]
+    pairs = torch.empty((ns, 2), dtype=torch.int64, device=dev)
+    nn_s = torch.empty(ns, dtype=torch.int32, device=dev)
+    nn_t = torch.empty(nt, dtype=torch.int32, device=dev) if mutual_filter else None
+    m = torch.zeros(1, dtype=torch.int64, device=dev)
+    L = N.lib()
+    with torch.cuda.device(dev):
+        ws = _workspace(0, 0, dev, need=L.slg_feature_match_ws_bytes(ns, nt))
+        _raise(L.slg_feature_match(E._vp(a), ns, E._vp(b), nt, int(bool(mutual_filter)), E._vp(ws), ws.numel(), E._vp(nn_s),
+                                   E._vp(nn_t) if nn_t is not None else None, E._vp(pairs), E._vp(m), E._stream(stream)))
+        count = int(m.item())
+    return pairs[:count], nn_s, nn_t
+
+
+def correspondences_from_features(source_feature, target_feature, mutual_filter: bool = False, stream=None) -> torch.Tensor:
+    """Open3D ``CorrespondencesFromFeatures``: device int64 ``[m, 2]`` (source row, target row) in
+    source order.  Per source row the target row with the smallest ``(d2, index)``,
+    ``d2 = sum_j (a_j - b_j)^2`` summed left to right, by exact brute force; with ``mutual_filter``
+    only the pairs the reverse search confirms."""
+    return feature_nearest(source_feature, target_feature, mutual_filter, stream)[0]
+
+
+def ransac_max_trials(confidence: float, ratio: float):
+    """``ceil(log(1 - confidence) / log(1 - ratio^3))``; ``0`` for ``ratio >= 1``; ``None`` where
+    the expression bounds nothing (``confidence`` 1, or a ratio whose cube vanishes beside 1)."""
+    if ratio >= 1.0:
+        return 0
+    den = math.log(1.0 - (ratio * ratio) * ratio)
+    if not den < 0.0 or confidence >= 1.0:
+        return None
+    return int(math.ceil(math.log(1.0 - confidence) / den))
+
+
+class RansacChoice:
+    """The sequential choice of the RANSAC, fed with the evaluated trials' records
+    in ascending trial order: a record replaces the best when its fitness is larger, or equal with
+    a smaller rmse (ties keep the earlier trial); on a replacement with
+    ``r = inliers / n_pairs > 0``, ``K = min(K, max(t + 1, ransac_max_trials(confidence, r)))``.
+    Records at or past ``K`` are ignored."""
+
+    def __init__(self, n_pairs: int, max_iteration: int, confidence: float):
+        self.n_pairs, self.confidence, self.K = int(n_pairs), float(confidence), int(max_iteration)
+        self.best = None            # the winner's record
+
+    def offer(self, rec) -> bool:
+        """False once the record lies at or past ``K`` (so do all later ones)."""
+        t = int(rec[0])
+        if t >= self.K:
+            return False
+        fitness, rmse = float(rec[22]), float(rec[23])
+        if self.best is None or fitness > self.best[22] or (fitness == self.best[22] and rmse < self.best[23]):
+            self.best = rec
+            r = float(rec[24]) / self.n_pairs
+            if r > 0.0:
+                k = ransac_max_trials(self.confidence, r)
+                if k is not None:
+                    self.K = min(self.K, max(t + 1, k))
+        return True
+
+
+def ransac_batch(source, target, pairs: torch.Tensor, max_correspondence_distance, first_trial: int, count: int,
+                 edge_length=0.9, confidence=0.999, seed=0, ransac_n=3, prepare=True, return_trials=False,
+                 corr_cap=0, max_eval=RANSAC_MAX_EVAL, stream=None):
+    """One batch of trials (``first_trial .. first_trial + count - 1``) on the device:
+    ``(records [n_eval, RANSAC_RECORD_STRIDE] NumPy, trials [count, RANSAC_TRIAL_STRIDE] NumPy or
+    None, corr int32 [min(n_eval, corr_cap), n_source] device or None, consumed)``.  At most
+    ``max_eval`` trials are evaluated; ``consumed`` is the number of trials the batch dealt with
+    (``count``, or up to the first passing trial left out, where the next batch starts).
+    ``prepare``: build the target's grid first (needed once per registration while nothing else
+    uses the workspace)."""
+    src, tgt = _check_xyz(as_point_cloud(source).xyz), _check_xyz(as_point_cloud(target).xyz)
+    dev = src.device
+    ns, nt, count = src.shape[0], tgt.shape[0], int(count)
+    pairs = pairs.to(device=dev, dtype=torch.int64).contiguous()
+    sd = int(seed) & 0xFFFFFFFFFFFFFFFF                      # the seed's 64 bits as the int64 the C ABI takes
+    sd = sd - (1 << 64) if sd >> 63 else sd
+    L = N.lib()
+    with torch.cuda.device(dev):
+        ws = _workspace(0, 0, dev, need=L.slg_ransac_ws_bytes(ns, nt, max(count, RANSAC_BATCH)))
+        if prepare:
+            _raise(L.slg_ransac_prepare(E._vp(tgt), nt, E._vp(ws), ws.numel(), E._stream(stream)))
+        records = torch.empty((count, N.RANSAC_RECORD_STRIDE), dtype=torch.float64, device=dev)
+        n_eval = torch.zeros(2, dtype=torch.int32, device=dev)
+        trials = torch.empty((count, N.RANSAC_TRIAL_STRIDE), dtype=torch.float64, device=dev) if return_trials else None
+        corr = torch.empty((int(corr_cap), ns), dtype=torch.int32, device=dev) if corr_cap else None
+        _raise(L.slg_ransac_batch(E._vp(src), ns, E._vp(tgt), nt, E._vp(pairs), pairs.shape[0], int(ransac_n),
+                                  float(edge_length), float(max_correspondence_distance), float(confidence),
+                                  sd, int(first_trial), count, E._vp(ws), ws.numel(), int(max_eval), E._vp(records),
+                                  E._vp(n_eval), E._vp(trials) if trials is not None else None,
+                                  E._vp(corr) if corr is not None else None, int(corr_cap), E._stream(stream)))
+        k, consumed = (int(v) for v in n_eval.cpu())
+        _check_status(ws, "registration_ransac_based_on_feature_matching")
+        return (records[:k].cpu().numpy(), trials.cpu().numpy() if trials is not None else None,
+                corr[:min(k, int(corr_cap))] if corr is not None else None, consumed)
+
+
+def registration_ransac_based_on_feature_matching(source, target, source_feature, target_feature, mutual_filter,
+                                                  max_correspondence_distance, ransac_n=3, edge_length=0.9,
+                                                  max_iteration=100000, confidence=0.999, seed=0,
+                                                  stream=None) -> RegistrationResult:
+    """Open3D ``registration_ransac_based_on_feature_matching(source, target, source_feature,
+    target_feature, mutual_filter, max_correspondence_distance,
+    TransformationEstimationPointToPoint(False), 3, [CorrespondenceCheckerBasedOnEdgeLength(
+    edge_length), CorrespondenceCheckerBasedOnDistance(max_correspondence_distance)],
+    RANSACConvergenceCriteria(max_iteration, confidence))`` on the device, as a pure function of the
+    clouds, the features and ``seed`` (``csrc/cloud_ransac.hip``; rules: DESIGN.md §13).
+
+    The correspondences come from :func:`correspondences_from_features` (without the mutual filter
+    when it leaves fewer than three).  The device runs the trials in batches of ``RANSAC_BATCH``
+    (a batch ends early once ``RANSAC_MAX_EVAL`` of its trials have passed both checkers); per
+    batch the records of the trials that passed are read back and :class:`RansacChoice` scans
+    them in trial order.  With no passing trial the result is the
+    identity with fitness 0."""
+    what = "registration_ransac_based_on_feature_matching"
+    source, target = as_point_cloud(source), as_point_cloud(target)
+    if not (source.has_points() and target.has_points()):
+        raise ValueError("Point cloud is empty.")
+    d, e, c, it = float(max_correspondence_distance), float(edge_length), float(confidence), int(max_iteration)
+    if not (d > 0.0 and math.isfinite(d)):
+        raise ValueError(f"{what}: max_correspondence_distance must be finite and > 0")
+    if not 0.0 <= e <= 1.0:
+        raise ValueError(f"{what}: edge_length must lie in [0, 1]")
+    if not 0.0 <= c <= 1.0:
+        raise ValueError(f"{what}: confidence must lie in [0, 1]")
+    if it < 0:
+        raise ValueError(f"{what}: max_iteration must be >= 0")
+    a, b = _check_features(source_feature, what), _check_features(target_feature, what)
+    if a.shape[0] != len(source) or b.shape[0] != len(target):
+        raise ValueError(f"{what}: one feature row per point is needed")
+    if int(ransac_n) != 3:
+        N.lib()
+        raise N.NativeError(N.SLG_ERR_UNSUPPORTED, f"{what}: ransac_n must be 3")
+    pairs = correspondences_from_features(a, b, bool(mutual_filter), stream)
+    if mutual_filter and len(pairs) < 3:
+        pairs = correspondences_from_features(a, b, False, stream)
+    choice = RansacChoice(len(pairs), it, c)
+    log, t0 = [], 0
+    while t0 < choice.K:
+        count = min(RANSAC_BATCH, it - t0)
+        records, _, _, consumed = ransac_batch(source, target, pairs, d, t0, count, e, c, seed, 3, prepare=t0 == 0,
+                                               stream=stream)
+        for rec in records:
+            if not choice.offer(rec):
+                break
+            log.append(rec)
+        t0 += consumed
+    log = np.stack(log) if log else np.zeros((0, N.RANSAC_RECORD_STRIDE))
+    if choice.best is None:
+        res = RegistrationResult(np.eye(4), 0.0, 0.0, choice.K, choice.K < it,
+                                 torch.zeros((0, 2), dtype=torch.int64, device=source.xyz.device), log)
+        res.trial = -1
+        return res
+    w = choice.best
+    T = w[4:20].reshape(4, 4).copy()
+    ev = evaluate_registration(source, target, d, T, stream)         # the winner's correspondences
+    res = RegistrationResult(T, float(w[22]), float(w[23]), choice.K, choice.K < it, ev.correspondence_set, log)
+    res.trial = int(w[0])
+    return res

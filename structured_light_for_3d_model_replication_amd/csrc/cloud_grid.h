@@ -2,7 +2,8 @@
 // workspace header, the sparse uniform grid's device helpers, the two neighbour walks, the top-k
 // lists, and the host functions of cloud_grid.hip.  Users: cloud_filter.hip (radius count,
 // statistical filter), cloud_cluster.hip (DBSCAN), cloud_normals.hip (voxel down-sample, normals),
-// cloud_icp.hip (point-to-plane ICP's correspondence search).
+// cloud_icp.hip (point-to-plane ICP's correspondence search), cloud_feature.hip (FPFH's neighbour
+// lists), cloud_ransac.hip (the evaluation of a batch of hypotheses).
 //
 // The grid: bbox (fixed-order reduction) -> integer cell coordinates floor((p - min) / cell)
 // packed into a 63-bit key (21 bits per axis, x lowest) -> stable radix sort of (key, index) ->
@@ -403,5 +404,27 @@ __device__ inline bool ring_walk(const Hdr* hdr, const double* __restrict__ sxyz
   const double p[3] = {sxyz[3 * q], sxyz[3 * q + 1], sxyz[3 * q + 2]};
   return ring_walk_at<kRadius, false>(hdr, sxyz, sidx, ukeys, ustart, p, r2, tk);
 }
+
+// ---------------------------------------------------------------- evaluating a transform
+// What the ICP (cloud_icp.hip) and the RANSAC's batched evaluation (cloud_ransac.hip) share.
+// PointCloud::Transform with a last row of 0 0 0 1: T is anything indexed 0..15, row-major.
+template <class M>
+__device__ inline void transform_point_rule(const M& T, const double* p, double* o) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) o[a] = ((T[4 * a] * p[0] + T[4 * a + 1] * p[1]) + T[4 * a + 2] * p[2]) + T[4 * a + 3];
+}
+
+// The correspondence of one query: the smallest (d2, target input index) among d2 < r2.  It has
+// the members the walks read of a list (kk, cnt, curmax) and is held in registers.
+struct Best1 {
+  int kk, cnt;
+  double curmax;
+  uint32_t idx;
+  __device__ inline void offer(double d, const uint32_t* __restrict__ sidx, size_t j) {
+    if (cnt && d > curmax) return;
+    const uint32_t i = sidx[j];
+    if (!cnt || pair_before_rule(d, i, curmax, idx)) { curmax = d; idx = i; cnt = 1; }
+  }
+};
 
 }  // namespace slgcloud

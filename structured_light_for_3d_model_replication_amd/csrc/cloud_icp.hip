@@ -56,31 +56,13 @@ size_t icp_layout(void* base, size_t grid_bytes, int64_t ns, int32_t max_iterati
 }
 
 // ---------------------------------------------------------------- the rules (one place each)
-// PointCloud::Transform with a last row of 0 0 0 1: T is anything indexed 0..15, row-major.
-template <class M>
-__device__ inline void transform_point_rule(const M& T, const double* p, double* o) {
-#pragma unroll
-  for (int a = 0; a < 3; ++a) o[a] = ((T[4 * a] * p[0] + T[4 * a + 1] * p[1]) + T[4 * a + 2] * p[2]) + T[4 * a + 3];
-}
+// (transform_point_rule and Best1, which cloud_ransac.hip shares, are in cloud_grid.h.)
 // Normals: the 3x3 block, no translation.
 template <class M>
 __device__ inline void transform_normal_rule(const M& T, const double* v, double* o) {
 #pragma unroll
   for (int a = 0; a < 3; ++a) o[a] = (T[4 * a] * v[0] + T[4 * a + 1] * v[1]) + T[4 * a + 2] * v[2];
 }
-
-// The correspondence of one query: the smallest (d2, target input index) among d2 < r2.  It has
-// the members the walks read of a list (kk, cnt, curmax) and is held in registers.
-struct Best1 {
-  int kk, cnt;
-  double curmax;
-  uint32_t idx;
-  __device__ inline void offer(double d, const uint32_t* __restrict__ sidx, size_t j) {
-    if (cnt && d > curmax) return;
-    const uint32_t i = sidx[j];
-    if (!cnt || pair_before_rule(d, i, curmax, idx)) { curmax = d; idx = i; cnt = 1; }
-  }
-};
 
 // Index of entry (a, b), a <= b, of a 6x6 upper triangle stored row by row.
 __host__ __device__ constexpr int ut(int a, int b) { return a * 6 - a * (a - 1) / 2 + (b - a); }

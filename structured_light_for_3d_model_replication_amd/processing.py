@@ -9,10 +9,12 @@ deterministic neighbour steps, which run on the device (``cloud.py``): ``remove_
 ``merge_pro_360`` (:605-628: voxel down-sample, uniform sample, outlier removal, normals) as
 ``merge_postprocess``, and the normal estimation and radial orientation that open
 ``reconstruct_stl`` and ``mesh_360`` (:653-670, :804-837) as ``estimate_oriented_normals``.
-``merge_pro_360`` itself (:489-629) runs on the device for scans whose initial poses are given:
-point-to-plane ICP, ``transform`` and ``+=``.  FPFH features, RANSAC global
-registration, tangent-plane orientation, Poisson, ball pivoting and RANSAC plane removal are out
-of scope.
+``merge_pro_360`` itself (:489-629) runs on the device: point-to-plane ICP, ``transform`` and
+``+=`` from initial poses that are given, or, with ``init_transforms="ransac"``,
+found as the reference finds them, by FPFH features and a seeded RANSAC global registration
+(``preprocess_point_cloud(..., features=True)``, ``execute_global_registration``).
+Tangent-plane orientation, Poisson, ball pivoting and RANSAC plane removal are out of scope
+(DESIGN.md §Scope).
 """
 from __future__ import annotations
 
@@ -480,34 +482,58 @@ class ProcessingLogic:
 
     # --- 360-degree merge (device; cloud.py) ---
     @staticmethod
-    def preprocess_point_cloud(pcd, voxel_size):
-        """Steps 1-2 of the reference's ``preprocess_point_cloud`` (``server/processing.py:451-468``)
-        on the device: voxel down-sample at ``voxel_size``, then normals with
-        ``radius = voxel_size * 2`` and ``max_nn = 30``.  Returns ``(pcd_down, None)``: there is no
-        FPFH here (step 3 feeds only the RANSAC this port leaves out), so ``None`` stands in its
-        place."""
+    def preprocess_point_cloud(pcd, voxel_size, features=False):
+        """The reference's ``preprocess_point_cloud`` (``server/processing.py:451-468``) on the
+        device: voxel down-sample at ``voxel_size``, normals with ``radius = voxel_size * 2`` and
+        ``max_nn = 30``, and, with ``features=True``, the FPFH features with
+        ``radius = voxel_size * 5`` and ``max_nn = 100`` (device float64 ``[n, 33]``).  Returns
+        ``(pcd_down, fpfh)``; without ``features`` (the default, for scans whose poses are known)
+        ``None`` stands in the feature's place."""
         from . import cloud as CL
         pcd_down = CL.voxel_down_sample(pcd, voxel_size)
         pcd_down = CL.estimate_normals(pcd_down, voxel_size * 2, 30)
-        return pcd_down, None
+        return pcd_down, (CL.compute_fpfh_feature(pcd_down, voxel_size * 5, 100) if features else None)
+
+    @staticmethod
+    def execute_global_registration(source_down, target_down, source_fpfh, target_fpfh, voxel_size, icp_dist_ratio=1.5,
+                                    seed=0):
+        """The reference's ``execute_global_registration`` (``server/processing.py:470-486``) on
+        the device with its fixed parameters: the mutual filter, the distance
+        ``voxel_size * icp_dist_ratio`` for the correspondences and the distance checker, three
+        points per trial, the edge-length checker at 0.9, and the criteria (100000, 0.999).  The
+        result is a function of the inputs and ``seed``."""
+        from . import cloud as CL
+        distance_threshold = voxel_size * icp_dist_ratio
+        return CL.registration_ransac_based_on_feature_matching(
+            source_down, target_down, source_fpfh, target_fpfh, True, distance_threshold, ransac_n=3, edge_length=0.9,
+            max_iteration=100000, confidence=0.999, seed=seed)
 
     @staticmethod
     def merge_pro_360(input_folder, output_path, voxel_size=0.02, icp_dist_ratio=1.5, outlier_nb=20, outlier_std=2.0,
-                      sample_before=1, sample_after=1, final_voxel=0.5, step_callback=None, init_transforms=None):
+                      sample_before=1, sample_after=1, final_voxel=0.5, step_callback=None, init_transforms=None,
+                      seed=0):
         """Sequential merge of a folder of per-view PLY files (``server/processing.py:489-629``)
-        on the device, for scans whose initial poses are known.
+        on the device.
 
         File discovery, the degree sort, the errors and the print lines are the reference's.  Per
         step both clouds are pre-processed (:meth:`preprocess_point_cloud`), the initial transform
-        of scan ``i`` onto scan ``i - 1`` is taken from ``init_transforms`` in place of the
-        reference's FPFH + RANSAC guess (a sequence of 4x4 matrices, entry ``i - 1`` for step
-        ``i``, or a callable ``(i, source_down, target_down) -> 4x4``; ``None``: the identity, for
-        scans already posed), point-to-plane ICP runs on the device with ``voxel_size`` as the
-        correspondence distance, the transform is accumulated, and the full-resolution source is
-        transformed and appended.  ``icp_dist_ratio`` only scaled the RANSAC distance and is
-        unused.  ``step_callback(i, total_steps, accumulated_cloud)`` gets a ``cloud.PointCloud``.
-        The tail is :meth:`merge_postprocess`; ``output_path`` is ASCII PLY with normals."""
+        of scan ``i`` onto scan ``i - 1`` is found, point-to-plane ICP runs on the device with
+        ``voxel_size`` as the correspondence distance, the transform is accumulated, and the
+        full-resolution source is transformed and appended.
+
+        ``init_transforms="ransac"`` finds the initial transform as the reference does: FPFH
+        features and :meth:`execute_global_registration` with the distance
+        ``voxel_size * icp_dist_ratio``, printing the reference's ``[RANSAC]`` lines.  Step ``i``
+        uses the seed ``seed + i``, so a merge is a function of its files and ``seed``.  Otherwise
+        the transform is taken from ``init_transforms`` (a sequence of 4x4 matrices, entry
+        ``i - 1`` for step ``i``, or a callable ``(i, source_down, target_down) -> 4x4``; ``None``:
+        the identity, for scans already posed) and ``icp_dist_ratio`` and ``seed`` are unused.
+        ``step_callback(i, total_steps, accumulated_cloud)`` gets a ``cloud.PointCloud``.  The tail
+        is :meth:`merge_postprocess`; ``output_path`` is ASCII PLY with normals."""
         from . import cloud as CL
+        use_ransac = isinstance(init_transforms, str)
+        if use_ransac and init_transforms != "ransac":
+            raise ValueError(f"init_transforms: {init_transforms!r} is not 'ransac', a sequence, a callable or None")
         print(f"[Merge 360] Loading clouds from {input_folder}...")
         ply_files = sorted(glob.glob(os.path.join(input_folder, "*.ply")), key=extract_degree)
         print(f"[Merge 360] Sorted file order:")
@@ -531,16 +557,25 @@ class ProcessingLogic:
         for i in range(1, len(pcds)):
             print(f"\n[Merge 360] === Step {i}/{total_steps}: Aligning Scan {i} -> Scan {i-1} ===")
             source, target = pcds[i], pcds[i - 1]
-            source_down, _ = ProcessingLogic.preprocess_point_cloud(source, voxel_size)
-            target_down, _ = ProcessingLogic.preprocess_point_cloud(target, voxel_size)
+            source_down, source_fpfh = ProcessingLogic.preprocess_point_cloud(source, voxel_size, features=use_ransac)
+            target_down, target_fpfh = ProcessingLogic.preprocess_point_cloud(target, voxel_size, features=use_ransac)
             print(f"  Preprocessed: source={len(source_down)} pts, target={len(target_down)} pts (voxel={voxel_size})")
-            if init_transforms is None:
-                init = np.identity(4)
-            elif callable(init_transforms):
-                init = init_transforms(i, source_down, target_down)
+            if use_ransac:
+                ransac_result = ProcessingLogic.execute_global_registration(
+                    source_down, target_down, source_fpfh, target_fpfh, voxel_size, icp_dist_ratio, seed=seed + i)
+                print(f"  [RANSAC] Fitness: {ransac_result.fitness:.4f} | RMSE: {ransac_result.inlier_rmse:.6f}")
+                if ransac_result.fitness < 0.05:
+                    print(f"  [WARNING] Step {i}: RANSAC fitness is very low ({ransac_result.fitness:.4f})! "
+                          f"Alignment may be unreliable. Try lowering Voxel Size or increasing ICP Dist Ratio.")
+                init = ransac_result.transformation
             else:
-                init = init_transforms[i - 1]
-            print("  [RANSAC] skipped: initial transform given")
+                if init_transforms is None:
+                    init = np.identity(4)
+                elif callable(init_transforms):
+                    init = init_transforms(i, source_down, target_down)
+                else:
+                    init = init_transforms[i - 1]
+                print("  [RANSAC] skipped: initial transform given")
             icp_result = CL.registration_icp(source_down, target_down, voxel_size, init)
             print(f"  [ICP]    Fitness: {icp_result.fitness:.4f} | RMSE: {icp_result.inlier_rmse:.6f}")
             if icp_result.fitness < 0.05:

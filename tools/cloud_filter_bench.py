@@ -29,6 +29,19 @@ reference's defaults (1e-6, 1e-6, 30), status and result read-back included; the
 tests/icp_ref.py over cKDTree with ``workers`` threads, and iterations, convergence, the final
 correspondences and the transform are compared.  ``--icp-only`` leaves everything else out.
 
+``--fpfh RADIUS MAX_NN`` and ``--global-reg DIST`` add the global registration,
+each stage between HIP events of its own: the FPFH features of the view (normals at radius
+``0.4 * RADIUS``, max_nn 30: the merge's relation between the two), the feature matching with the
+mutual filter, and the seeded RANSAC.  The registration is of a moved part of the view (as in
+tests/feature_ref.py's base case: the points with ``index % 3 != 1`` and x above the 20 %
+quantile, under the inverse of a rotation of (25, -10, 15) degrees about the centroid plus a
+translation of about ``5 * DIST``, with its own normals and features) onto the view.  The host side is
+tests/feature_ref.py: features from cKDTree-proposed lists are compared for equality where the
+proposal resolved every tie; the brute-force matching restatement is not affordable at a whole
+view (1.2 M x 1.2 M rows), so ``--match-sample`` rows (default 64) are compared and the count
+is reported; the RANSAC restatement runs on the device's correspondences.  ``--gr-only`` leaves
+every other step out.
+
 Prints one JSON line.
 """
 from __future__ import annotations
@@ -60,6 +73,12 @@ def main():
     ap.add_argument("--skip-cluster", action="store_true", help="leave the cluster step out")
     ap.add_argument("--icp", type=float, metavar="DIST", help="also time the point-to-plane ICP at this distance")
     ap.add_argument("--icp-only", action="store_true", help="with --icp: leave every other step out")
+    ap.add_argument("--fpfh", nargs=2, metavar=("RADIUS", "MAX_NN"), help="also time the FPFH features and the matching")
+    ap.add_argument("--global-reg", type=float, metavar="DIST",
+                    help="with --fpfh: also time the RANSAC registration of a moved copy at this distance")
+    ap.add_argument("--match-sample", type=int, default=64, help="rows of the matching compared with the restatement")
+    ap.add_argument("--seed", type=int, default=0, help="the RANSAC's seed")
+    ap.add_argument("--gr-only", action="store_true", help="with --fpfh: leave every other step out")
     args = ap.parse_args()
 
     import numpy as np
@@ -124,6 +143,75 @@ def main():
                 "max_transform_difference_cpu": float(np.abs(ref["T"] - reg.transformation).max()),
                 "speedup_vs_cpu": cpu_ms / (sum(ms) / args.steps)})
         if args.icp_only:
+            print(json.dumps(res))
+            return
+    if args.global_reg and not args.fpfh:
+        raise SystemExit("--global-reg needs --fpfh RADIUS MAX_NN")
+    if args.fpfh:
+        import feature_ref as FR
+        import icp_ref as IR
+        import normals_ref as NR
+        fr, fk = float(args.fpfh[0]), int(args.fpfh[1])
+        tgt = CL.estimate_normals(pc, 0.4 * fr, 30)
+        (ft, _, fm), ms = timed(lambda: CL.fpfh_features(tgt, fr, fk))
+        print(f"[device] fpfh done {ms}", file=sys.stderr, flush=True)
+        res["fpfh"] = {"radius": fr, "max_nn": fk, "normal_radius": 0.4 * fr, "device_ms": ms,
+                       "whole_cloud_points": CL.far_count(pc.xyz.device), "capped": float((fm == fk).double().mean().item()),
+                       "alone": int((fm <= 1).sum().item()),
+                       "workspace_bytes": int(CL.N.lib().slg_fpfh_ws_bytes(n, fk))}
+        P = pc.xyz.cpu().numpy()
+        d = float(args.global_reg) if args.global_reg else 0.0
+        T_true = IR.motion_about(P.mean(0), FR.BASE_ANGLES_DEG, 5.0 * d * np.array([1.0, -0.7, 0.4]))
+        part = torch.from_numpy((np.arange(n) % 3 != 1) & (P[:, 0] > np.quantile(P[:, 0], 0.2))).to(pc.xyz.device)
+        moved = CL.transform(CL.PointCloud(pc.xyz[part], pc.bgr[part]), IR.inverse_rigid(T_true))
+        src = CL.estimate_normals(moved, 0.4 * fr, 30)
+        fs = CL.compute_fpfh_feature(src, fr, fk)
+        (pairs, nn_s, nn_t), ms = timed(lambda: CL.feature_nearest(fs, ft, True))
+        mean_ms = sum(ms) / args.steps
+        print(f"[device] match done {ms}", file=sys.stderr, flush=True)
+        res["match"] = {"source_rows": len(src), "target_rows": n, "mutual_pairs": len(pairs), "device_ms": ms,
+                        "fp64_ops": 2 * 66.0 * len(src) * n, "fp64_tflops": 2 * 66.0 * len(src) * n / (mean_ms * 1e-3) / 1e12}
+        if args.global_reg:
+            reg, ms = timed(lambda: CL.registration_ransac_based_on_feature_matching(src, tgt, fs, ft, True, d, seed=args.seed))
+            S = src.xyz.cpu().numpy()
+            print(f"[device] global registration done {ms}", file=sys.stderr, flush=True)
+            res["global_reg"] = {"dist": d, "seed": args.seed, "device_ms": ms, "winner_trial": reg.trial, "K": reg.iterations,
+                                 "evaluated_trials": len(reg.log), "fitness": reg.fitness, "inlier_rmse": reg.inlier_rmse,
+                                 "whole_target_queries": CL.far_count(pc.xyz.device),
+                                 "motion_error": IR.motion_error(reg.transformation, T_true, S)}
+        if not args.no_cpu:
+            N_t = tgt.normals.cpu().numpy()
+            t0 = time.perf_counter()
+            idx, dd, resolved = NR.neighbour_lists_tree(P, fk, workers=args.workers)
+            ref = FR.compute_fpfh(P, N_t, fr, fk, (idx, dd))
+            cpu_ms = (time.perf_counter() - t0) * 1e3
+            # a point's feature needs its own list and its neighbours' lists resolved
+            ok = resolved & np.all(resolved[ref["idx"]] | ~ref["inside"], axis=1)
+            dft = ft.cpu().numpy()
+            res["fpfh"].update({
+                "cpu_ms": cpu_ms, "cpu_what": f"tests/feature_ref.py, lists proposed by scipy cKDTree(workers={args.workers})",
+                "unresolved_ties_cpu": int((~ok).sum()), "edge_bin_pairs_cpu": ref["edge_pairs"],
+                "m_equal_cpu": bool(np.array_equal(fm.cpu().numpy()[resolved], ref["m"][resolved])),
+                "fpfh_equal_cpu": bool(np.array_equal(dft[ok].view(np.uint64), ref["fpfh"][ok].view(np.uint64))),
+                "rows_differing_cpu": int((dft[ok] != ref["fpfh"][ok]).any(1).sum()),
+                "speedup_vs_cpu": cpu_ms / (sum(res["fpfh"]["device_ms"]) / args.steps)})
+            print("[cpu] fpfh done", file=sys.stderr, flush=True)
+            dfs = fs.cpu().numpy()
+            rows = np.linspace(0, len(dfs) - 1, min(args.match_sample, len(dfs))).astype(np.int64)
+            t0 = time.perf_counter()
+            want = FR.nearest_rows_brute(dfs[rows], dft)
+            res["match"].update({"cpu_sample_rows": len(rows), "cpu_sample_ms": (time.perf_counter() - t0) * 1e3,
+                                 "sample_equal_cpu": bool(np.array_equal(nn_s.cpu().numpy()[rows], want))})
+            if args.global_reg:
+                t0 = time.perf_counter()
+                rr = FR.ransac(S, P, pairs.cpu().numpy(), d, seed=args.seed, workers=args.workers)
+                cpu_ms = (time.perf_counter() - t0) * 1e3
+                res["global_reg"].update({
+                    "cpu_ms": cpu_ms, "cpu_what": "tests/feature_ref.py ransac on the device's correspondences",
+                    "winner_and_K_equal_cpu": bool((rr["trial"], rr["K"]) == (reg.trial, reg.iterations)),
+                    "max_transform_difference_cpu": float(np.abs(rr["T"] - reg.transformation).max()),
+                    "speedup_vs_cpu": cpu_ms / (sum(res["global_reg"]["device_ms"]) / args.steps)})
+        if args.gr_only:
             print(json.dumps(res))
             return
     (rad, rad_idx), ms = timed(lambda: CL.radius_outlier(pc, 100, 5.0, return_index=True))
