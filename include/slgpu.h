@@ -657,6 +657,56 @@ int32_t slg_ransac_batch(const double *src_xyz, int64_t n_source, const double *
                          double *records_out, int32_t *n_eval_out, double *trials_out,
                          int32_t *corr_out, int32_t corr_cap, void *stream);
 
+/* ---- Seeded RANSAC plane segmentation on the device cloud (csrc/cloud_plane.hip):
+ * PointCloud.segment_plane of ProcessingLogic.remove_background (server/processing.py:337-364).
+ * Open3D's published rules restated (places where the rule is ours are marked so in DESIGN.md),
+ * fp64, no floating-point atomics: the same cloud and seed give the same bits.  Asynchronous on
+ * `stream`; the status word at the front of ws as for the filters (a NaN or infinite coordinate
+ * sets SLG_FILTER_BAD_NONFINITE; the outputs are then unspecified).  xyz must be 16-byte aligned.
+ *
+ *   slg_plane_batch
+ * runs the trials first_trial .. first_trial + batch - 1.  Trial t draws ransac_n indices
+ * (((h >> 32) * n) >> 32 with h = mix(mix(seed + 0x9E3779B97F4A7C15) + 8 t + k), mix the finaliser
+ * of SplitMix64); two equal draws make the trial invalid.  ransac_n = 3: abc = (p1 - p0) x (p2 - p0),
+ * norm = sqrt((x^2 + y^2) + z^2), invalid when 0, else abc / norm and d = -((a p0x + b p0y) + c p0z).
+ * ransac_n > 3: the centroid (sum in draw order / ransac_n), the six centred sums xx xy xz yy yz zz
+ * in draw order, det_x = yy zz - yz yz, det_y = xx zz - xz xz, det_z = xx yy - xy xy; abc =
+ * (det_x, xz yz - xy zz, xy yz - xz yy) when det_x is strictly the largest, else
+ * (xz yz - xy zz, det_y, xy xz - yz xx) when det_y > det_z, else (xy yz - xz yy, xy xz - yz xx,
+ * det_z); normalised as above with d from the centroid.  Every trial is evaluated over the whole
+ * cloud: dist = |((a x + b y) + c z) + d|, an inlier when dist < distance_threshold (strict),
+ * count their number, err the sum of their dist: left to right within each chunk of 2048
+ * consecutive points (a point that is no inlier adds +0.0), then the chunks left to right.
+ * records_out float64 [batch][SLG_PLANE_RECORD_STRIDE], one record per trial in trial order:
+ * trial, valid, a, b, c, d, count, err, fitness = count / n, rmse = err / sqrt(count) (0 without
+ * inliers), 6 unused; an invalid trial has the zero plane and zeros.  The choice among the records
+ * is sequential in the trial number and is the host's (cloud.py).
+ *
+ *   slg_plane_finish
+ * takes a plane (HOST float64 [4]): index_out int64 [n] gets the indices with dist <
+ * distance_threshold in ascending order, *count_out (DEVICE int64) their number m; sums_out
+ * (DEVICE float64 [SLG_PLANE_SUMS_LEN]): the sums of x, y, z over those points, the six centred
+ * sums xx xy xz yy yz zz about centroid = sums / m, the centroid (3), m, 3 unused, each sum the
+ * fixed tree of slg_cloud_centroid over the input order in which other points add nothing;
+ * plane_out (DEVICE float64 [4]): the ransac_n > 3 rule applied to that centroid and those sums.
+ *
+ * ws: slg_plane_ws_bytes(n, batch) bytes (slg_plane_finish needs batch = 1).  SLG_ERR_INVALID for
+ * n <= 0, n < ransac_n, ransac_n < 3, batch <= 0, first_trial < 0, a threshold or plane that is not
+ * finite (and > 0), a NULL or misaligned buffer or a workspace that is too small;
+ * SLG_ERR_UNSUPPORTED above 2^30 points, ransac_n > SLG_PLANE_MAX_RANSAC_N or batch >
+ * SLG_PLANE_MAX_BATCH. */
+#define SLG_PLANE_MAX_BATCH 4096
+#define SLG_PLANE_RECORD_STRIDE 16
+#define SLG_PLANE_SUMS_LEN 16
+#define SLG_PLANE_MAX_RANSAC_N 8
+int64_t slg_plane_ws_bytes(int64_t n, int32_t batch);
+int32_t slg_plane_batch(const double *xyz, int64_t n, double distance_threshold, int32_t ransac_n,
+                        int64_t seed, int64_t first_trial, int32_t batch, void *ws, int64_t ws_bytes,
+                        double *records_out, void *stream);
+int32_t slg_plane_finish(const double *xyz, int64_t n, const double *plane, double distance_threshold,
+                         void *ws, int64_t ws_bytes, int64_t *index_out, int64_t *count_out,
+                         double *sums_out, double *plane_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,7 +166,11 @@ EXPORTS = {
     "slg_ransac_prepare": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp]),
     "slg_ransac_batch": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_dbl, c_dbl, c_dbl, c_i64, c_i64,
                                  c_i32, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "slg_plane_ws_bytes": (c_i64, [c_i64, c_i32]),
+    "slg_plane_batch": (c_i32, [c_vp, c_i64, c_dbl, c_i32, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp]),
+    "slg_plane_finish": (c_i32, [c_vp, c_i64, ctypes.POINTER(c_dbl), c_dbl, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
+PLANE_MAX_BATCH, PLANE_RECORD_STRIDE, PLANE_SUMS_LEN, PLANE_MAX_RANSAC_N = 4096, 16, 16, 8
 FILTER_BAD_NONFINITE, FILTER_BAD_EXTENT, FILTER_BAD_INDEX = 1, 2, 4
 FPFH_DIM, FPFH_MAX_NN = 33, 128                  # SLG_FPFH_DIM, SLG_FPFH_MAX_NN
 RANSAC_MAX_BATCH, RANSAC_TRIAL_STRIDE, RANSAC_RECORD_STRIDE = 16384, 20, 32

@@ -20,6 +20,9 @@ The loop body of ``merge_pro_360`` (``:549-603``) has its deterministic part her
 :func:`registration_ransac_based_on_feature_matching` (``server/processing.py:451-486``;
 DESIGN.md §13).
 
+The cleanup tab's first step, ``ProcessingLogic.remove_background`` (``:337-364``), is here as the
+seeded :func:`segment_plane` and :func:`remove_plane`.
+
 The PLY reader takes exactly the file ``ProcessingLogic._save_ply`` writes (``ply.header``): ASCII,
 ``x y z red green blue``, or the same with ``nx ny nz`` after ``z`` (a cloud with normals).
 Anything else raises ``ValueError`` saying what differs.
@@ -785,3 +788,179 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
     res = RegistrationResult(T, float(w[22]), float(w[23]), choice.K, choice.K < it, ev.correspondence_set, log)
     res.trial = int(w[0])
     return res
+
+
+# ----------------------------------------------------------------------------- plane segmentation
+PLANE_BATCH = 256           # trials per slg_plane_batch: one workgroup column of the evaluation, one read-back each
+PLANE_PROBABILITY = 0.99999999      # Open3D's default
+
+
+def plane_max_trials(probability: float, fitness: float, ransac_n: int):
+    """``ceil(log(1 - probability) / log(1 - fitness^ransac_n))`` with the power by repeated
+    multiplication; ``None`` where the expression bounds nothing (``probability`` 1, or a
+    denominator that is not ``< 0``).  For ``0 < fitness < 1``."""
+    p = fitness
+    for _ in range(int(ransac_n) - 1):
+        p = p * fitness
+    den = math.log(1.0 - p)
+    if not den < 0.0 or probability >= 1.0:
+        return None
+    return int(math.ceil(math.log(1.0 - probability) / den))
+
+
+class PlaneChoice:
+    """The sequential choice of the plane RANSAC, a sibling of :class:`RansacChoice`,
+    fed with every trial's record in ascending trial order: a valid record replaces the best when
+    its fitness is larger, or equal with a smaller rmse (ties keep the earlier trial); on a
+    replacement, ``fitness == 1`` gives ``K = min(K, t + 1)`` and ``0 < fitness < 1`` gives
+    ``K = min(K, max(t + 1, plane_max_trials(probability, fitness, ransac_n)))``.  Records at or
+    past ``K`` are ignored."""
+
+    def __init__(self, num_iterations: int, probability: float, ransac_n: int):
+        self.K, self.probability, self.ransac_n = int(num_iterations), float(probability), int(ransac_n)
+        self.best = None            # the winner's record
+
+    def offer(self, rec) -> bool:
+        """False once the record lies at or past ``K`` (so do all later ones)."""
+        t = int(rec[0])
+        if t >= self.K:
+            return False
+        if rec[1] == 0.0:
+            return True
+        fitness, rmse = float(rec[8]), float(rec[9])
+        if self.best is None or fitness > self.best[8] or (fitness == self.best[8] and rmse < self.best[9]):
+            self.best = rec
+            if fitness >= 1.0:
+                self.K = min(self.K, t + 1)
+            elif fitness > 0.0:
+                k = plane_max_trials(self.probability, fitness, self.ransac_n)
+                if k is not None:
+                    self.K = min(self.K, max(t + 1, k))
+        return True
+
+
+class PlaneSegmentation(tuple):
+    """What :func:`segment_plane` returns: the pair ``(plane_model, inliers)`` (NumPy ``[4]``,
+    device int64 ascending), which also carries ``trial`` (the winner's trial number, -1: no valid
+    trial), ``iterations`` (the final ``K``), ``log`` (NumPy ``[*, PLANE_RECORD_STRIDE]``: the
+    record of every trial below ``K``), ``sample_plane`` (the winner's own plane, before the refit),
+    ``fitness`` and ``inlier_rmse`` of the winner, and ``sums`` (NumPy ``[PLANE_SUMS_LEN]``: the
+    refit's nine sums, centroid and count, or ``None``)."""
+
+    def __new__(cls, plane_model, inliers, trial, iterations, log, sample_plane, fitness, inlier_rmse, sums):
+        self = super().__new__(cls, (plane_model, inliers))
+        self.plane_model, self.inliers = plane_model, inliers
+        self.trial, self.iterations, self.log = trial, iterations, log
+        self.sample_plane, self.fitness, self.inlier_rmse, self.sums = sample_plane, fitness, inlier_rmse, sums
+        return self
+
+
+def _seed_i64(seed) -> int:
+    sd = int(seed) & 0xFFFFFFFFFFFFFFFF                      # the seed's 64 bits as the int64 the C ABI takes
+    return sd - (1 << 64) if sd >> 63 else sd
+
+
+def _plane_xyz(pc) -> torch.Tensor:
+    xyz = _check_xyz(as_point_cloud(pc).xyz)
+    return xyz if xyz.data_ptr() % 16 == 0 else xyz.clone()      # the evaluation stages with 16-byte loads
+
+
+def plane_batch(pc, distance_threshold, first_trial: int, count: int, ransac_n=3, seed=0, stream=None) -> np.ndarray:
+    """One batch of trials (``first_trial .. first_trial + count - 1``) on the device: their
+    records, NumPy ``[count, PLANE_RECORD_STRIDE]`` (one read-back)."""
+    xyz = _plane_xyz(pc)
+    n, dev, count = xyz.shape[0], xyz.device, int(count)
+    L = N.lib()
+    with torch.cuda.device(dev):
+        ws = _workspace(0, 0, dev, need=L.slg_plane_ws_bytes(n, max(count, PLANE_BATCH)))
+        records = torch.empty((count, N.PLANE_RECORD_STRIDE), dtype=torch.float64, device=dev)
+        _raise(L.slg_plane_batch(E._vp(xyz), n, float(distance_threshold), int(ransac_n), _seed_i64(seed), int(first_trial),
+                                 count, E._vp(ws), ws.numel(), E._vp(records), E._stream(stream)))
+        host = records.cpu().numpy()
+        _check_status(ws, "segment_plane")
+    return host
+
+
+def plane_finish(pc, plane, distance_threshold, stream=None):
+    """``(inliers int64 device ascending, sums NumPy [PLANE_SUMS_LEN], refitted plane NumPy [4])``
+    of a plane: the points with ``dist < distance_threshold`` and ``GetPlaneFromPoints`` over them."""
+    xyz = _plane_xyz(pc)
+    n, dev = xyz.shape[0], xyz.device
+    pl = np.ascontiguousarray(np.asarray(plane, np.float64).reshape(4))
+    L = N.lib()
+    with torch.cuda.device(dev):
+        ws = _workspace(0, 0, dev, need=L.slg_plane_ws_bytes(n, PLANE_BATCH))
+        index = torch.empty(n, dtype=torch.int64, device=dev)
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
+        out = torch.zeros(N.PLANE_SUMS_LEN + 4, dtype=torch.float64, device=dev)
+        _raise(L.slg_plane_finish(E._vp(xyz), n, _dbl16(pl), float(distance_threshold), E._vp(ws), ws.numel(), E._vp(index),
+                                  E._vp(count), E._vp(out), E._vp(out[N.PLANE_SUMS_LEN:]), E._stream(stream)))
+        host = out.cpu().numpy()
+        m = int(count.item())
+        _check_status(ws, "segment_plane")
+    return index[:m], host[:N.PLANE_SUMS_LEN].copy(), host[N.PLANE_SUMS_LEN:].copy()
+
+
+def segment_plane(pc, distance_threshold, ransac_n=3, num_iterations=100, probability=PLANE_PROBABILITY, seed=0,
+                  stream=None) -> PlaneSegmentation:
+    """Open3D ``PointCloud.segment_plane(distance_threshold, ransac_n, num_iterations, probability)``
+    on the device, as a pure function of the cloud and ``seed`` (``csrc/cloud_plane.hip``; rules:
+    DESIGN.md §14): ``(plane_model, inliers)`` with the plane refitted over the inliers.
+
+    The device runs the trials in batches of ``PLANE_BATCH``; per batch every trial's record is
+    read back and :class:`PlaneChoice` scans them in trial order.  With no valid trial the result
+    is the plane ``(0, 0, 0, 0)`` with no inliers.  ``3 <= ransac_n <= 8``."""
+    what = "segment_plane"
+    pc = as_point_cloud(pc)
+    if not pc.has_points():
+        raise ValueError("Point cloud is empty.")
+    d, rn, it, pr = float(distance_threshold), int(ransac_n), int(num_iterations), float(probability)
+    if rn < 3:
+        raise ValueError(f"{what}: ransac_n must be >= 3")
+    if len(pc) < rn:
+        raise ValueError(f"{what}: the cloud has fewer points than ransac_n")
+    if not (d > 0.0 and math.isfinite(d)):
+        raise ValueError(f"{what}: distance_threshold must be finite and > 0")
+    if it < 0:
+        raise ValueError(f"{what}: num_iterations must be >= 0")
+    if not 0.0 < pr <= 1.0:
+        raise ValueError(f"{what}: probability must lie in (0, 1]")
+    if rn > N.PLANE_MAX_RANSAC_N:
+        N.lib()
+        raise N.NativeError(N.SLG_ERR_UNSUPPORTED, f"{what}: ransac_n must be <= {N.PLANE_MAX_RANSAC_N}")
+    choice = PlaneChoice(it, pr, rn)
+    log, t0 = [], 0
+    while t0 < choice.K:
+        count = min(PLANE_BATCH, choice.K - t0)
+        for rec in plane_batch(pc, d, t0, count, rn, seed, stream):
+            if not choice.offer(rec):
+                break
+            log.append(rec)
+        t0 += count
+    log = np.stack(log) if log else np.zeros((0, N.PLANE_RECORD_STRIDE))
+    if choice.best is None:
+        return PlaneSegmentation(np.zeros(4), torch.zeros(0, dtype=torch.int64, device=pc.xyz.device), -1, choice.K, log,
+                                 np.zeros(4), 0.0, 0.0, None)
+    w = choice.best
+    inliers, sums, plane = plane_finish(pc, w[2:6], d, stream)
+    return PlaneSegmentation(plane, inliers, int(w[0]), choice.K, log, w[2:6].copy(), float(w[8]), float(w[9]), sums)
+
+
+def remove_plane(pc, distance_threshold, ransac_n=3, num_iterations=1000, seed=0):
+    """``segment_plane`` + ``select_by_index(inliers, invert=True)``: ``(the cloud without the
+    plane's inliers, the segmentation)``.  Colours are kept, and normals when present; with no
+    inliers the input cloud itself comes back."""
+    pc = as_point_cloud(pc)
+    seg = segment_plane(pc, distance_threshold, ransac_n, num_iterations, seed=seed)
+    if len(seg.inliers) == 0:
+        return pc, seg
+    keep = torch.ones(len(pc), dtype=torch.uint8, device=pc.xyz.device)
+    keep[seg.inliers] = 0
+    if len(seg.inliers) == len(pc):
+        dev = pc.xyz.device
+        return PointCloud(torch.empty((0, 3), dtype=torch.float64, device=dev), torch.empty((0, 3), dtype=torch.uint8, device=dev),
+                          normals=None), seg
+    out, idx = select(pc, keep)
+    if pc.has_normals():
+        out.normals = pc.normals[idx].contiguous()
+    return out, seg

@@ -395,6 +395,28 @@ class ProcessingLogic:
         return CL.as_point_cloud(input_data)
 
     @staticmethod
+    def remove_background(input_data, output_path=None, distance_threshold=50, ransac_n=3, num_iterations=1000,
+                          return_obj=False, seed=0):
+        """Back-wall removal on the device (``server/processing.py:337-364``): the seeded RANSAC
+        plane segmentation of ``cloud.segment_plane``, then the cloud without the
+        plane's inliers, with its colours (and normals, when it has them).
+
+        The reference's signature plus ``seed`` (the result is a pure function of the cloud and
+        the seed), its print lines and exceptions; the same two differences from the reference as
+        :meth:`remove_outliers`."""
+        from . import cloud as CL
+        print(f"[BG Remove] Processing...")
+        pcd = ProcessingLogic._load_pcd(input_data)
+        if not pcd.has_points():
+            raise ValueError("Point cloud is empty.")
+        object_cloud, _ = CL.remove_plane(pcd, distance_threshold, ransac_n, num_iterations, seed=seed)
+        print(f"[BG Remove] Original: {len(pcd)}, Remaining: {len(object_cloud)} pts")
+        if output_path:
+            ProcessingLogic._save_ply(*object_cloud.numpy(), output_path)
+            print(f"[BG Remove] Saved to {output_path}")
+        return object_cloud if return_obj else None
+
+    @staticmethod
     def remove_outliers(input_data, output_path=None, nb_neighbors=20, std_ratio=2.0, return_obj=False):
         """Statistical outlier removal on the device (``server/processing.py:367-388``).
 

@@ -42,6 +42,15 @@ view (1.2 M x 1.2 M rows), so ``--match-sample`` rows (default 64) are compared 
 is reported; the RANSAC restatement runs on the device's correspondences.  ``--gr-only`` leaves
 every other step out.
 
+``--plane DIST [ITERATIONS]`` adds the seeded RANSAC plane segmentation on the
+view's cloud with a planted wall behind it (tests/plane_ref.py's ``plant_wall``: as many points
+again on a tilted plane ``4 * DIST`` behind the farthest point, offsets below ``DIST / 2``).  HIP
+events go around one batch's launches alone (trials, evaluation, records), around a batch with
+its read-back, around the finish, and around the whole ``segment_plane`` and ``remove_plane``; the
+per-kernel split comes from a kernel trace of the same command.  The host side is
+tests/plane_ref.py on ``workers`` threads; the winner, ``K``, every record's bits and the inlier
+set are compared.  ``--plane-only`` leaves every other step out.
+
 Prints one JSON line.
 """
 from __future__ import annotations
@@ -79,6 +88,9 @@ def main():
     ap.add_argument("--match-sample", type=int, default=64, help="rows of the matching compared with the restatement")
     ap.add_argument("--seed", type=int, default=0, help="the RANSAC's seed")
     ap.add_argument("--gr-only", action="store_true", help="with --fpfh: leave every other step out")
+    ap.add_argument("--plane", nargs="+", metavar="DIST [ITERATIONS]",
+                    help="also time the plane segmentation at this distance threshold (default 1000 iterations)")
+    ap.add_argument("--plane-only", action="store_true", help="with --plane: leave every other step out")
     args = ap.parse_args()
 
     import numpy as np
@@ -111,6 +123,57 @@ def main():
 
     res = {"tool": "cloud_filter_bench", "points": n, "row_mode": args.row_mode, "cam": [W, H],
            "steps": args.steps, "device": torch.cuda.get_device_name(0)}
+    if args.plane:
+        import plane_ref as PR
+        d = float(args.plane[0])
+        iters = int(args.plane[1]) if len(args.plane) > 1 else 1000
+        P0, C0 = pc.numpy()
+        nrm = np.array(PR.WALL_NORMAL) / np.linalg.norm(PR.WALL_NORMAL)
+        along = (P0 - P0.mean(0)) @ nrm
+        side = int(np.sqrt(n))
+        pitch = float(np.ptp(P0, axis=0).max()) / side
+        P, wall = PR.plant_wall(P0, behind=float(along.max()) + 4.0 * d, grid=(side, side), pitch=pitch, jitter=0.5 * d)
+        wpc = CL.PointCloud(P, np.concatenate([C0, np.full((int(wall.sum()), 3), 200, np.uint8)]))
+        nw, dev = len(wpc), wpc.xyz.device
+        L, B = CL.N.lib(), CL.PLANE_BATCH
+        ws = CL._workspace(0, 0, dev, need=L.slg_plane_ws_bytes(nw, B))
+        recs = torch.empty((B, CL.N.PLANE_RECORD_STRIDE), dtype=torch.float64, device=dev)
+
+        def launch():                                        # the batch's three kernels, no read-back
+            CL._raise(L.slg_plane_batch(E._vp(wpc.xyz), nw, d, 3, args.seed, 0, B, E._vp(ws), ws.numel(), E._vp(recs),
+                                        E._stream(None)))
+        _, ms_launch = timed(launch)
+        _, ms_batch = timed(lambda: CL.plane_batch(wpc, d, 0, B, 3, args.seed))
+        seg, ms = timed(lambda: CL.segment_plane(wpc, d, 3, iters, seed=args.seed))
+        _, ms_finish = timed(lambda: CL.plane_finish(wpc, seg.sample_plane, d))
+        (obj, _), ms_remove = timed(lambda: CL.remove_plane(wpc, d, 3, iters, seed=args.seed))
+        evals = float(B) * nw
+        mean_launch = sum(ms_launch) / args.steps
+        res["plane"] = {
+            "dist": d, "num_iterations": iters, "seed": args.seed, "points": nw, "wall_points": int(wall.sum()), "batch": B,
+            "device_segment_ms": ms, "device_batch_launch_ms": ms_launch, "device_batch_with_readback_ms": ms_batch,
+            "device_finish_ms": ms_finish, "device_remove_plane_ms": ms_remove,
+            "winner_trial": seg.trial, "K": seg.iterations, "fitness": seg.fitness, "inliers": len(seg.inliers),
+            "inliers_are_the_wall": bool(np.array_equal(seg.inliers.cpu().numpy(), np.flatnonzero(wall))),
+            "remaining": len(obj), "plane": seg.plane_model.tolist(),
+            # per evaluation: 3 mul + 3 add for the distance, 1 add for err (|.|, the compare, the select and the
+            # integer count are not floating-point operations)
+            "evaluations_per_batch": evals, "fp64_ops_per_evaluation": 7,
+            "evaluations_per_s_from_batch_launch": evals / (mean_launch * 1e-3),
+            "fp64_tflops_from_batch_launch": 7.0 * evals / (mean_launch * 1e-3) / 1e12}
+        if not args.no_cpu:
+            t0 = time.perf_counter()
+            ref = PR.segment(P, d, 3, iters, seed=args.seed, workers=args.workers)
+            cpu_ms = (time.perf_counter() - t0) * 1e3
+            res["plane"].update({
+                "cpu_ms": cpu_ms, "cpu_what": f"tests/plane_ref.py segment, {args.workers} threads",
+                "winner_and_K_equal_cpu": bool((ref["trial"], ref["K"]) == (seg.trial, seg.iterations)),
+                "records_equal_cpu": bool(np.array_equal(np.stack(ref["records"]).view(np.uint64), seg.log.view(np.uint64))),
+                "inliers_equal_cpu": bool(np.array_equal(ref["inliers"], seg.inliers.cpu().numpy())),
+                "speedup_vs_cpu": cpu_ms / (sum(ms) / args.steps)})
+        if args.plane_only:
+            print(json.dumps(res))
+            return
     if args.icp:
         import icp_ref as IR
         d = float(args.icp)
