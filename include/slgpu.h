@@ -353,8 +353,11 @@ int32_t slg_png_read(const char *path, uint8_t *gray, int64_t gray_cap, uint8_t 
  * [height][out_pitch] rows of width * channels bytes).  status is DEVICE int32 [2 * n]:
  * status[2f] = 0 or SLG_PNG_E_* (a frame with a non-zero status is left unspecified and must
  * be decoded on the host), status[2f + 1] internal.  Asynchronous on `stream`; returns 0 or SLG_ERR_*. */
-#define SLG_PNG_E_STREAM 1     /* not a valid zlib/deflate stream (or reads past zlen) */
-#define SLG_PNG_E_SIZE 2       /* inflated size differs from height * (1 + width * channels) */
+#define SLG_PNG_E_STREAM 1     /* not a valid zlib/deflate stream (or reads past zlen); also a stored
+                                  block longer than what is left of the image (its LEN is refused
+                                  before any of its bytes is taken) */
+#define SLG_PNG_E_SIZE 2       /* inflated size differs from height * (1 + width * channels): the
+                                  stream ends short, or a literal or a copy would pass the end */
 #define SLG_PNG_E_ADLER 3      /* Adler-32 of the inflated bytes differs from the stream's */
 #define SLG_PNG_E_FILTER 4     /* a scanline filter type byte > 4 */
 #define SLG_PNG_E_UNSUPPORTED 5 /* rows wider than the device un-filter takes (width * channels > 24576) */

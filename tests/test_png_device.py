@@ -5,7 +5,8 @@ an encoder may emit: stored, fixed-Huffman and dynamic blocks (zlib levels 0-9, 
 Z_RLE and Z_HUFFMAN_ONLY strategies), all five row filters chosen per row (Average too, which
 PIL's adaptive filter rarely picks), copies closer than 64 bytes, gray / RGB / RGBA, ragged and
 tiny sizes.  A stream corrupted behind a valid chunk CRC must come back with a non-zero status
-(the host then decodes that view)."""
+(the host then decodes that view).  What the decoder accepts and refuses beyond one encoder's
+habits is stated by the stream table of ``deflate_cases.py`` (``test_png_device_streams.py``)."""
 import ctypes
 import os
 import struct
