@@ -710,6 +710,64 @@ int32_t slg_plane_finish(const double *xyz, int64_t n, const double *plane, doub
                          void *ws, int64_t ws_bytes, int64_t *index_out, int64_t *count_out,
                          double *sums_out, double *plane_out, void *stream);
 
+/* ---- Tangent-plane normal orientation on the device cloud (csrc/cloud_orient.hip):
+ * PointCloud.orient_normals_consistent_tangent_plane(k) of mesh_360 and reconstruct_stl
+ * (server/processing.py:675, :685, :823), with the neighbour lists and the Euclidean minimum
+ * spanning tree it is built from as calls of their own.  Open3D's procedure in closed form (its
+ * sort leaves ties open; the total orders below are ours), fp64, integer atomics only: the same
+ * input gives the same bits.  Asynchronous on `stream`; the status word at the front of ws as for
+ * the filters (a NaN or infinite coordinate or normal sets SLG_FILTER_BAD_NONFINITE; the outputs
+ * are then unspecified).
+ *
+ *   slg_knn_lists
+ * kk = min(k, n) entries per point: all points in ascending (d2, input index) order, d2 =
+ * (dx^2 + dy^2) + dz^2, the point itself included (it is first unless a duplicate with a lower
+ * index precedes it).  idx_out uint32 [n][kk], d2_out float64 [n][kk], rows by input index.
+ *
+ *   slg_emst
+ * the minimum spanning tree of the complete graph under the total order (d2, a, b) on the
+ * undirected edges (a, b), a < b: unique, duplicates are ordinary edges with d2 = 0.  edges_out
+ * int64 [n - 1][2] gets its edges (a, b) in no particular order.  k is the length of the lists
+ * the Boruvka rounds start from (any k >= 1 gives the same tree).
+ *
+ *   slg_orient_tangent
+ * the Riemannian graph is the EMST's edges and, for every point, the edges to its list entries
+ * other than itself; its minimum spanning tree under (w, a, b), w = 1 - |(na.x nb.x + na.y nb.y)
+ * + na.z nb.z|, is unique.  The root is the lowest index among the points of largest z; its normal
+ * is negated iff its z component is negative.  Every other point's sign is the root's times the
+ * product over its tree path of sgn(na . nb) on the input normals, sgn(0) = +1.  normals_out
+ * float64 [n][3] (not the input buffer) gets the normals, negated as a whole or left alone;
+ * optional: emst_out and tree_out int64 [n - 1][2] as above, root_out int64 [1].
+ *
+ * stats_out (optional, DEVICE int32 [SLG_ORIENT_STATS_LEN]): SLG_ORIENT_STAT_*: the rounds of the
+ * two Boruvkas, the points the lists sent to the whole-cloud kernel, the points that walked the
+ * grid for a foreign neighbour and the far-list entries (totals, then per EMST round from
+ * SLG_ORIENT_STAT_ROUND_*), and the rounds the largest component sat out.  These depend on the
+ * schedule, the results do not.
+ *
+ * ws: slg_orient_ws_bytes(n, k) bytes.  SLG_ERR_INVALID for n <= 0, k <= 0, a NULL or misaligned
+ * (8 bytes) buffer, normals_out == normals or a workspace that is too small; SLG_ERR_UNSUPPORTED
+ * above 2^30 points or k > SLG_ORIENT_MAX_K. */
+#define SLG_ORIENT_MAX_K 128
+#define SLG_ORIENT_STATS_LEN 128
+#define SLG_ORIENT_STAT_EMST_ROUNDS 0
+#define SLG_ORIENT_STAT_TREE_ROUNDS 1
+#define SLG_ORIENT_STAT_LIST_FAR 2
+#define SLG_ORIENT_STAT_WALKED 3
+#define SLG_ORIENT_STAT_FAR 4
+#define SLG_ORIENT_STAT_SAT_OUT 5
+#define SLG_ORIENT_STAT_ROUND_WALKED 16
+#define SLG_ORIENT_STAT_ROUND_FAR 48
+#define SLG_ORIENT_STAT_ROUND_SAT_OUT 80
+int64_t slg_orient_ws_bytes(int64_t n, int32_t k);
+int32_t slg_knn_lists(const double *xyz, int64_t n, int32_t k, void *ws, int64_t ws_bytes,
+                      uint32_t *idx_out, double *d2_out, void *stream);
+int32_t slg_emst(const double *xyz, int64_t n, int32_t k, void *ws, int64_t ws_bytes,
+                 int64_t *edges_out, int32_t *stats_out, void *stream);
+int32_t slg_orient_tangent(const double *xyz, const double *normals, int64_t n, int32_t k, void *ws,
+                           int64_t ws_bytes, double *normals_out, int64_t *emst_out, int64_t *tree_out,
+                           int64_t *root_out, int32_t *stats_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

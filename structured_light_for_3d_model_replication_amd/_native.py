@@ -169,7 +169,16 @@ EXPORTS = {
     "slg_plane_ws_bytes": (c_i64, [c_i64, c_i32]),
     "slg_plane_batch": (c_i32, [c_vp, c_i64, c_dbl, c_i32, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp]),
     "slg_plane_finish": (c_i32, [c_vp, c_i64, ctypes.POINTER(c_dbl), c_dbl, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "slg_orient_ws_bytes": (c_i64, [c_i64, c_i32]),
+    "slg_knn_lists": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "slg_emst": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "slg_orient_tangent": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
+ORIENT_MAX_K, ORIENT_STATS_LEN = 128, 128        # SLG_ORIENT_MAX_K, SLG_ORIENT_STATS_LEN
+# SLG_ORIENT_STAT_*: indices into the stats of slg_emst / slg_orient_tangent
+(ORIENT_STAT_EMST_ROUNDS, ORIENT_STAT_TREE_ROUNDS, ORIENT_STAT_LIST_FAR, ORIENT_STAT_WALKED, ORIENT_STAT_FAR,
+ ORIENT_STAT_SAT_OUT) = range(6)
+ORIENT_STAT_ROUND_WALKED, ORIENT_STAT_ROUND_FAR, ORIENT_STAT_ROUND_SAT_OUT = 16, 48, 80
 PLANE_MAX_BATCH, PLANE_RECORD_STRIDE, PLANE_SUMS_LEN, PLANE_MAX_RANSAC_N = 4096, 16, 16, 8
 FILTER_BAD_NONFINITE, FILTER_BAD_EXTENT, FILTER_BAD_INDEX = 1, 2, 4
 FPFH_DIM, FPFH_MAX_NN = 33, 128                  # SLG_FPFH_DIM, SLG_FPFH_MAX_NN

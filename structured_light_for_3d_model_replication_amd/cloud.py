@@ -964,3 +964,118 @@ def remove_plane(pc, distance_threshold, ransac_n=3, num_iterations=1000, seed=0
     if pc.has_normals():
         out.normals = pc.normals[idx].contiguous()
     return out, seg
+
+
+# ----------------------------------------------------------------------------- tangent-plane orientation
+EMST_LIST_K = 16            # length of the lists euclidean_mst's rounds start from (the tree does not depend on it)
+
+
+def _orient_ws(n: int, k: int, device) -> torch.Tensor:
+    return _workspace(0, 0, device, need=N.lib().slg_orient_ws_bytes(n, k))
+
+
+def _check_k(k, what: str) -> int:
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"{what}: k must be >= 1")
+    return k
+
+
+def _sorted_edges(edges: torch.Tensor) -> torch.Tensor:
+    """The rows ``(a, b)``, ``a < b < 2^31``, in ascending ``(a, b)`` order."""
+    if edges.shape[0] == 0:
+        return edges
+    key, _ = torch.sort(edges[:, 0] * (1 << 32) + edges[:, 1])
+    return torch.stack((key >> 32, key & 0xFFFFFFFF), dim=1)
+
+
+def knn_lists_raw(pc, k: int, stream=None):
+    """``(idx int32 [n, kk], d2 float64 [n, kk])``, ``kk = min(k, n)``, on the device: for every
+    point all points in ascending ``(d2, input index)`` order, the point itself included."""
+    pc = as_point_cloud(pc)
+    if not pc.has_points():
+        raise ValueError("Point cloud is empty.")
+    k = _check_k(k, "knn_lists")
+    xyz = _check_xyz(pc.xyz)
+    n, dev = xyz.shape[0], xyz.device
+    kk = min(k, n)
+    idx = torch.empty((n, kk), dtype=torch.int32, device=dev)
+    d2 = torch.empty((n, kk), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        ws = _orient_ws(n, k, dev)
+        _raise(N.lib().slg_knn_lists(E._vp(xyz), n, k, E._vp(ws), ws.numel(), E._vp(idx), E._vp(d2), E._stream(stream)))
+        _check_status(ws, "knn_lists")
+    return idx, d2
+
+
+def knn_lists(pc, k: int, stream=None):
+    """``(idx int32 [n, k'], d2 float64 [n, k'])``, ``k' = min(k, n) - 1``, on the device: the first
+    ``min(k, n)`` points in ascending ``(d2, input index)`` order with the point itself removed
+    (Open3D's ``search_knn`` as the orientation uses it).  A row in which the point is not among
+    those (``min(k, n)`` or more duplicates with lower indices) loses its last entry instead."""
+    idx, d2 = knn_lists_raw(pc, k, stream)
+    n, kk = idx.shape
+    keep = idx != torch.arange(n, dtype=torch.int32, device=idx.device)[:, None]
+    keep[:, kk - 1] &= ~keep.all(dim=1)
+    return idx[keep].reshape(n, kk - 1), d2[keep].reshape(n, kk - 1)
+
+
+def nearest_neighbor_distance(pc, stream=None) -> torch.Tensor:
+    """Open3D ``compute_nearest_neighbor_distance``: float64 ``[n]`` on the device, the distance to
+    the nearest other point (``0`` for a cloud of fewer than two points)."""
+    pc = as_point_cloud(pc)
+    if len(pc) < 2:
+        return torch.zeros(len(pc), dtype=torch.float64, device=pc.xyz.device)
+    return torch.sqrt(knn_lists(pc, 2, stream)[1][:, 0])
+
+
+def euclidean_mst(pc, return_stats: bool = False, list_k: int = EMST_LIST_K, stream=None):
+    """The Euclidean minimum spanning tree under the total edge order ``(d2, a, b)``: int64
+    ``[n - 1, 2]`` on the device, rows ``(a, b)`` with ``a < b`` in ascending order.  With
+    ``return_stats`` also the int32 ``[ORIENT_STATS_LEN]`` counters of the rounds (host)."""
+    pc = as_point_cloud(pc)
+    if not pc.has_points():
+        raise ValueError("Point cloud is empty.")
+    k = _check_k(list_k, "euclidean_mst")
+    xyz = _check_xyz(pc.xyz)
+    n, dev = xyz.shape[0], xyz.device
+    buf = torch.empty((max(n - 1, 1), 2), dtype=torch.int64, device=dev)     # never a NULL buffer
+    stats = torch.zeros(N.ORIENT_STATS_LEN, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        ws = _orient_ws(n, k, dev)
+        _raise(N.lib().slg_emst(E._vp(xyz), n, k, E._vp(ws), ws.numel(), E._vp(buf), E._vp(stats), E._stream(stream)))
+        _check_status(ws, "euclidean_mst")
+    edges = _sorted_edges(buf[:n - 1])
+    return (edges, stats.cpu().numpy()) if return_stats else edges
+
+
+def orient_normals_consistent_tangent_plane(pc, k: int, return_tree: bool = False, stream=None):
+    """Open3D ``orient_normals_consistent_tangent_plane(k)`` on the device
+    (``csrc/cloud_orient.hip``; rules: DESIGN.md §15): a new ``PointCloud`` sharing ``xyz`` /
+    ``bgr`` whose normals are the input's, each negated as a whole or left alone.  ``1 <= k <=
+    128``; a cloud without normals raises ``RuntimeError`` as Open3D does.  With ``return_tree``:
+    ``(cloud, tree int64 [n - 1, 2], root int, info)`` with the Riemannian tree's edges in
+    ascending ``(a, b)`` order and ``info = {"emst": edges, "stats": int32 counters}``."""
+    pc = as_point_cloud(pc)
+    if not pc.has_points():
+        raise ValueError("Point cloud is empty.")
+    if not pc.has_normals():
+        raise RuntimeError("orient_normals_consistent_tangent_plane: the cloud has no normals (estimate_normals)")
+    k = _check_k(k, "orient_normals_consistent_tangent_plane")
+    xyz = _check_xyz(pc.xyz)
+    n, dev = xyz.shape[0], xyz.device
+    nrm = pc.normals.contiguous()
+    out = torch.empty_like(nrm)
+    emst = torch.empty((n - 1, 2), dtype=torch.int64, device=dev)            # optional outputs: a single point has none
+    tree = torch.empty((n - 1, 2), dtype=torch.int64, device=dev)
+    root = torch.zeros(1, dtype=torch.int64, device=dev)
+    stats = torch.zeros(N.ORIENT_STATS_LEN, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        ws = _orient_ws(n, k, dev)
+        _raise(N.lib().slg_orient_tangent(E._vp(xyz), E._vp(nrm), n, k, E._vp(ws), ws.numel(), E._vp(out), E._vp(emst),
+                                          E._vp(tree), E._vp(root), E._vp(stats), E._stream(stream)))
+        _check_status(ws, "orient_normals_consistent_tangent_plane")
+    res = PointCloud(pc.xyz, pc.bgr, normals=out)
+    if not return_tree:
+        return res
+    return res, _sorted_edges(tree), int(root.item()), {"emst": _sorted_edges(emst), "stats": stats.cpu().numpy()}

@@ -3,7 +3,8 @@
 // lists, and the host functions of cloud_grid.hip.  Users: cloud_filter.hip (radius count,
 // statistical filter), cloud_cluster.hip (DBSCAN), cloud_normals.hip (voxel down-sample, normals),
 // cloud_icp.hip (point-to-plane ICP's correspondence search), cloud_feature.hip (FPFH's neighbour
-// lists), cloud_ransac.hip (the evaluation of a batch of hypotheses).
+// lists), cloud_ransac.hip (the evaluation of a batch of hypotheses), cloud_orient.hip (the kNN
+// lists and the EMST's walks of the tangent-plane orientation).
 //
 // The grid: bbox (fixed-order reduction) -> integer cell coordinates floor((p - min) / cell)
 // packed into a 63-bit key (21 bits per axis, x lowest) -> stable radix sort of (key, index) ->

@@ -615,24 +615,47 @@ class ProcessingLogic:
 
     @staticmethod
     def estimate_oriented_normals(input_data, save_normals_path=None, normal_radius=0.1, normal_max_nn=30,
-                                  outward=True, return_obj=False):
-        """Steps 1-2b of ``mesh_360`` in radial mode (``server/processing.py:804-837``) on the
-        device; the reference has no stand-alone method for them.  Normals by the hybrid search
-        (``normal_radius``, ``normal_max_nn``), oriented towards the cloud's centre and then, with
-        ``outward``, negated; with ``normal_radius=10`` this is ``reconstruct_stl``'s centroid
-        branch (``:653-670``).  Raises ``FileNotFoundError`` for a missing path and
-        ``ValueError("Point cloud is empty.")`` as the reference does.  ``save_normals_path`` is
-        written as ASCII PLY with normals."""
+                                  outward=True, return_obj=False, orientation_mode="radial", tangent_k=100,
+                                  consistency_pass=False, consistency_k=30):
+        """Steps 1-2b of ``mesh_360`` (``server/processing.py:804-837``) on the device; the
+        reference has no stand-alone method for them.  Normals by the hybrid search
+        (``normal_radius``, ``normal_max_nn``), then, by ``orientation_mode``: ``"radial"``: oriented
+        towards the cloud's centre and then, with ``outward``, negated (with ``normal_radius=10``
+        this is ``reconstruct_stl``'s centroid branch, ``:653-670``); ``"tangent"``: the reference's
+        default, ``orient_normals_consistent_tangent_plane(tangent_k)`` (``:823``, ``:675``), with
+        the reference's fall-back to radial when that raises.  ``consistency_pass`` runs the
+        tangent-plane orientation once more afterwards with ``consistency_k`` neighbours (30 when
+        not positive), as ``reconstruct_stl`` does (``:682-686``).  Raises ``FileNotFoundError`` for
+        a missing path, ``ValueError("Point cloud is empty.")`` as the reference does, and
+        ``ValueError`` for an unknown mode.  ``save_normals_path`` is written as ASCII PLY with
+        normals."""
         from . import cloud as CL
+        if orientation_mode not in ("radial", "tangent"):
+            raise ValueError(f"orientation_mode must be 'radial' or 'tangent', not {orientation_mode!r}")
+        if orientation_mode == "tangent" and int(tangent_k) < 1:
+            raise ValueError("tangent_k must be >= 1")
         pcd = ProcessingLogic._load_pcd(input_data)
         if not pcd.has_points():
             raise ValueError("Point cloud is empty.")
         print(f"[360 Mesh] Estimating normals (radius={normal_radius}, max_nn={normal_max_nn})...")
         pcd = CL.estimate_normals(pcd, normal_radius, normal_max_nn)
-        print(f"[360 Mesh] Re-orienting normals (Mode: radial)...")
-        pcd = CL.orient_normals_towards(pcd, CL.centroid(pcd), outward=outward)
-        if outward:
-            print("[360 Mesh] Radial orientation applied (Outwards).")
+        print(f"[360 Mesh] Re-orienting normals (Mode: {orientation_mode})...")
+        if orientation_mode == "tangent":
+            try:
+                pcd = CL.orient_normals_consistent_tangent_plane(pcd, int(tangent_k))
+                print("[360 Mesh] Consistent tangent plane orientation applied.")
+            except Exception as e:
+                print(f"[360 Mesh] Warning: Tangent plane failed ({e}). Fallback to radial.")
+                pcd = CL.orient_normals_towards(pcd, CL.centroid(pcd), outward=True)
+        else:
+            pcd = CL.orient_normals_towards(pcd, CL.centroid(pcd), outward=outward)
+            if outward:
+                print("[360 Mesh] Radial orientation applied (Outwards).")
+        if consistency_pass:
+            k = int(consistency_k) if consistency_k > 0 else 30
+            print(f"[Recon] Consistency pass: orient_normals_consistent_tangent_plane(k={k})...")
+            pcd = CL.orient_normals_consistent_tangent_plane(pcd, k)
+            print("[Recon] Consistency pass applied.")
         if save_normals_path:
             print(f"[360 Mesh] Saving normals point cloud to {save_normals_path}...")
             pcd.save(save_normals_path)

@@ -51,6 +51,17 @@ per-kernel split comes from a kernel trace of the same command.  The host side i
 tests/plane_ref.py on ``workers`` threads; the winner, ``K``, every record's bits and the inlier
 set are compared.  ``--plane-only`` leaves every other step out.
 
+``--orient K`` adds the tangent-plane normal orientation: normals of the view at
+``--orient-normals RADIUS MAX_NN`` (default 5.0 30), a seeded random half of them negated, then
+``orient_normals_consistent_tangent_plane(K)``.  HIP events go around the whole call and around
+the calls that end after its first and second stage (``slg_knn_lists``, ``slg_emst``), so the three
+stages are differences; the counters of the rounds (rounds per Boruvka, points that walked and
+far-list entries per round) come from the call itself.  The host side is tests/orient_ref.py with
+the EMST's candidates from ``scipy.spatial.Delaunay``, which is valid only without cospherical
+ties: it runs on the view voxel-down-sampled to at most ``--orient-cpu-points`` points (the size is
+recorded), the device runs on that cloud too, and the tool asserts that the trees agree.
+``--orient-only`` leaves every other step out.
+
 Prints one JSON line.
 """
 from __future__ import annotations
@@ -91,6 +102,11 @@ def main():
     ap.add_argument("--plane", nargs="+", metavar="DIST [ITERATIONS]",
                     help="also time the plane segmentation at this distance threshold (default 1000 iterations)")
     ap.add_argument("--plane-only", action="store_true", help="with --plane: leave every other step out")
+    ap.add_argument("--orient", type=int, metavar="K", help="also time the tangent-plane normal orientation with K neighbours")
+    ap.add_argument("--orient-normals", nargs=2, default=("5.0", "30"), metavar=("RADIUS", "MAX_NN"),
+                    help="with --orient: the normal estimation before it")
+    ap.add_argument("--orient-cpu-points", type=int, default=20000, help="with --orient: the size the host side runs at")
+    ap.add_argument("--orient-only", action="store_true", help="with --orient: leave every other step out")
     args = ap.parse_args()
 
     import numpy as np
@@ -123,6 +139,68 @@ def main():
 
     res = {"tool": "cloud_filter_bench", "points": n, "row_mode": args.row_mode, "cam": [W, H],
            "steps": args.steps, "device": torch.cuda.get_device_name(0)}
+    if args.orient:
+        import orient_ref as OR
+        NAT = CL.N
+        k = int(args.orient)
+        nr, nk = float(args.orient_normals[0]), int(args.orient_normals[1])
+
+        def half_negated(cloud):
+            nrm = cloud.normals.clone()
+            flip = torch.from_numpy(np.random.default_rng(args.seed).random(len(cloud)) < 0.5).to(nrm.device)
+            nrm[flip] = -nrm[flip]
+            return CL.PointCloud(cloud.xyz, cloud.bgr, normals=nrm)
+
+        with_n = CL.estimate_normals(pc, nr, nk)
+        src = half_negated(with_n)
+        _, ms_lists = timed(lambda: CL.knn_lists_raw(src, k))
+        print(f"[device] lists done {ms_lists}", file=sys.stderr, flush=True)
+        _, ms_emst = timed(lambda: CL.euclidean_mst(src, list_k=k))
+        print(f"[device] EMST done {ms_emst}", file=sys.stderr, flush=True)
+        (out, tree, root, info), ms = timed(lambda: CL.orient_normals_consistent_tangent_plane(src, k, return_tree=True))
+        print(f"[device] orientation done {ms}", file=sys.stderr, flush=True)
+        st = info["stats"]
+        mean = lambda v: sum(v) / len(v)
+        rounds = int(st[NAT.ORIENT_STAT_EMST_ROUNDS])
+        plain = CL.orient_normals_consistent_tangent_plane(with_n, k)
+        res["orient"] = {
+            "k": k, "normal_radius": nr, "normal_max_nn": nk, "seed": args.seed, "points": n,
+            "device_ms": ms, "device_lists_ms": ms_lists, "device_lists_and_emst_ms": ms_emst,
+            "stage_lists_ms": mean(ms_lists), "stage_emst_ms": mean(ms_emst) - mean(ms_lists),
+            "stage_tree_and_signs_ms": mean(ms) - mean(ms_emst),
+            "what_is_timed": "each line: the call with its output allocation, edge sort, status and counter read-back",
+            "emst_rounds": rounds, "tree_rounds": int(st[NAT.ORIENT_STAT_TREE_ROUNDS]),
+            "lists_whole_cloud_points": int(st[NAT.ORIENT_STAT_LIST_FAR]),
+            "walked_per_round": st[NAT.ORIENT_STAT_ROUND_WALKED:NAT.ORIENT_STAT_ROUND_WALKED + rounds].tolist(),
+            "far_per_round": st[NAT.ORIENT_STAT_ROUND_FAR:NAT.ORIENT_STAT_ROUND_FAR + rounds].tolist(),
+            "largest_sat_out_per_round": st[NAT.ORIENT_STAT_ROUND_SAT_OUT:NAT.ORIENT_STAT_ROUND_SAT_OUT + rounds].tolist(),
+            "root": root, "negated": int((out.normals[:, 0] != src.normals[:, 0]).sum().item()),
+            "equal_to_the_run_without_negation": bool(torch.equal(out.normals, plain.normals)),
+            "workspace_bytes": int(NAT.lib().slg_orient_ws_bytes(n, k))}
+        if not args.no_cpu:
+            voxel, small = 0.0, pc
+            while len(small) > args.orient_cpu_points:
+                voxel = 1.0 if voxel == 0.0 else voxel * 1.25
+                small = CL.voxel_down_sample(pc, voxel)
+            small = half_negated(CL.estimate_normals(small, max(nr, 2.5 * voxel), nk))
+            (s_out, s_tree, s_root, s_info), s_ms = timed(
+                lambda: CL.orient_normals_consistent_tangent_plane(small, k, return_tree=True))
+            P, Nrm = small.xyz.cpu().numpy(), small.normals.cpu().numpy()
+            t0 = time.perf_counter()
+            want, w_tree, w_root, w_emst, _ = OR.orient(P, Nrm, k, emst=OR.emst_delaunay(P))
+            cpu_ms = (time.perf_counter() - t0) * 1e3
+            same = {"emst": bool(np.array_equal(s_info["emst"].cpu().numpy(), w_emst)),
+                    "tree": bool(np.array_equal(s_tree.cpu().numpy(), w_tree)), "root": s_root == w_root,
+                    "normals": bool(np.array_equal(s_out.normals.cpu().numpy().view(np.uint64), want.view(np.uint64)))}
+            res["orient"].update({
+                "cpu_points": len(small), "cpu_voxel": voxel, "cpu_ms": cpu_ms, "device_ms_at_cpu_points": s_ms,
+                "cpu_what": "tests/orient_ref.py: brute-force lists, Kruskal over scipy Delaunay candidates and over the "
+                            "Riemannian edges, queue traversal (one thread)",
+                "equal_cpu": same, "speedup_vs_cpu_at_cpu_points": cpu_ms / mean(s_ms)})
+            assert all(same.values()), f"the device and the Delaunay-based restatement differ: {same}"
+        if args.orient_only:
+            print(json.dumps(res))
+            return
     if args.plane:
         import plane_ref as PR
         d = float(args.plane[0])
