@@ -768,6 +768,85 @@ int32_t slg_orient_tangent(const double *xyz, const double *normals, int64_t n, 
                            int64_t ws_bytes, double *normals_out, int64_t *emst_out, int64_t *tree_out,
                            int64_t *root_out, int32_t *stats_out, void *stream);
 
+/* ---- Watertight meshing of an oriented device cloud on a dense uniform grid (csrc/cloud_mesh.hip;
+ * DESIGN.md §16): the last call of mesh_360 and reconstruct_stl(mode="watertight")
+ * (server/processing.py:703, :842).  Our rule, Open3D parity unpinned: the idea of Poisson surface
+ * reconstruction on a uniform grid of R = 2^depth cells per axis instead of Kazhdan's adaptive
+ * octree.  fp64, integer atomics only (the status word): the same input gives the same bits.
+ * Asynchronous on `stream`.  Node arrays are float64 [R+1]^3, x fastest.
+ *
+ * Every call takes a workspace, 256-byte aligned, whose first SLG_MESH_HDR_BYTES bytes are the
+ * header: int32 status (SLG_FILTER_BAD_* as for the filters) at byte 0, int32 R at 4, int64 nV at 8,
+ * int64 nT at 16, float64 origin[3] at 24, h at 48, iso at 56, thr at 64.  The rest is the stage's
+ * scratch, slg_mesh_ws_bytes(stage, R, n, m) bytes in all (n points or values, m triangles);
+ * SLG_MESH_WS_ALL: the largest of the stages GRID..EXTRACT plus the six node arrays W, V, f, chi
+ * (48 (R+1)^3 bytes), what a whole reconstruction holds.  Once the status word is set, later
+ * kernels return at once.
+ *
+ *   slg_mesh_grid        side = scale * largest extent of the box, origin = (min + max) / 2 -
+ *                        side / 2, h = side / R into the header; a non-finite coordinate or a zero
+ *                        extent sets the status word.
+ *   slg_mesh_set_header  the header from host values instead (the stages as calls of their own).
+ *   slg_mesh_splat       u = (p - origin) / h, i = floor(u) clamped to 0..R-1, t = u - i; per node
+ *                        its 8 incident cells in ascending cell id, each cell's points in
+ *                        ascending input index: W += w, V += w * normal, w the trilinear weight.
+ *                        V_out float64 [R+1]^3 x 3.  A non-finite normal sets the status word.
+ *   slg_mesh_divergence  f = (dVx / 2h + dVy / 2h) + dVz / 2h by central differences, 0 on the boundary.
+ *   slg_mesh_solve       the 7-point Laplacian of chi = f, chi = 0 on the boundary: `cycles` V(2,2)
+ *                        cycles from 0 of a vertex-centred multigrid R, R/2, .., 2; damped Jacobi
+ *                        (6/7), full weighting, trilinear prolongation, the R = 2 level directly.
+ *   slg_mesh_sample      out[j] = trilinear field at xyz[j].
+ *   slg_mesh_iso         header iso = mean of trilinear chi at the points (slg_cloud_centroid's tree).
+ *   slg_mesh_count       marching tetrahedra over Kuhn's six tetrahedra per cell, inside = chi < iso:
+ *                        crossing masks, triangle counts and their scans into the scratch; header
+ *                        nV, nT.  slg_mesh_emit (same workspace, untouched in between) then writes
+ *                        vertices float64 [nV][3] in ascending (owner node, edge type), densities
+ *                        (trilinear W at the vertex; W may be NULL) and triangles int32 [nT][3] in
+ *                        ascending (cell, tetrahedron, triangle), wound so that (b - a) x (c - a)
+ *                        points from inside to outside.
+ *   slg_mesh_quantile    header thr = numpy's linear quantile(values, q).
+ *   slg_mesh_remove      drops the vertices with mask != 0 and every triangle with such a corner,
+ *                        renumbers, keeps the order; header nV, nT are the new counts.
+ *   slg_mesh_triangle_normals  unit (b - a) x (c - a), (0, 0, 0) for a zero-area triangle.
+ *   slg_mesh_stl_pack    50 bytes per triangle: float32 normal, three float32 vertices, uint16 0.
+ *
+ * SLG_ERR_INVALID for a NULL or misaligned buffer, a count <= 0, depth outside 2..10, R no power
+ * of two in range, scale < 1, q outside [0, 1] or a workspace that is too small;
+ * SLG_ERR_UNSUPPORTED above 2^30 points or from 2^31 vertices. */
+#define SLG_MESH_HDR_BYTES 256
+#define SLG_MESH_WS_GRID 0
+#define SLG_MESH_WS_SPLAT 1
+#define SLG_MESH_WS_SOLVE 2
+#define SLG_MESH_WS_ISO 3
+#define SLG_MESH_WS_EXTRACT 4
+#define SLG_MESH_WS_QUANTILE 5
+#define SLG_MESH_WS_REMOVE 6
+#define SLG_MESH_WS_ALL 7
+int64_t slg_mesh_ws_bytes(int32_t stage, int32_t R, int64_t n, int64_t m);
+int32_t slg_mesh_set_header(void *ws, int32_t R, const double *origin, double h, double iso, void *stream);
+int32_t slg_mesh_grid(const double *xyz, int64_t n, int32_t depth, double scale, void *ws, int64_t ws_bytes,
+                      void *stream);
+int32_t slg_mesh_splat(const double *xyz, const double *normals, int64_t n, int32_t R, void *ws,
+                       int64_t ws_bytes, double *W_out, double *V_out, void *stream);
+int32_t slg_mesh_divergence(const double *V, int32_t R, void *ws, double *f_out, void *stream);
+int32_t slg_mesh_solve(const double *f, int32_t R, int32_t cycles, void *ws, int64_t ws_bytes,
+                       double *chi_out, void *stream);
+int32_t slg_mesh_sample(const double *field, const double *xyz, int64_t n, void *ws, double *out, void *stream);
+int32_t slg_mesh_iso(const double *chi, const double *xyz, int64_t n, void *ws, int64_t ws_bytes, void *stream);
+int32_t slg_mesh_count(const double *chi, int32_t R, void *ws, int64_t ws_bytes, void *stream);
+int32_t slg_mesh_emit(const double *chi, const double *W, int32_t R, void *ws, int64_t ws_bytes,
+                      double *vertices_out, int64_t n_vertices, double *densities_out, int32_t *triangles_out,
+                      int64_t n_triangles, void *stream);
+int32_t slg_mesh_quantile(const double *values, int64_t n, double q, void *ws, int64_t ws_bytes, void *stream);
+int32_t slg_mesh_remove(const double *vertices, const double *densities, int64_t n_vertices,
+                        const int32_t *triangles, int64_t n_triangles, const uint8_t *mask, void *ws,
+                        int64_t ws_bytes, double *vertices_out, double *densities_out, int32_t *triangles_out,
+                        void *stream);
+int32_t slg_mesh_triangle_normals(const double *vertices, const int32_t *triangles, int64_t n_triangles,
+                                  double *normals_out, void *stream);
+int32_t slg_mesh_stl_pack(const double *vertices, const int32_t *triangles, const double *normals,
+                          int64_t n_triangles, uint8_t *records_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -173,7 +173,25 @@ EXPORTS = {
     "slg_knn_lists": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "slg_emst": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "slg_orient_tangent": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "slg_mesh_ws_bytes": (c_i64, [c_i32, c_i32, c_i64, c_i64]),
+    "slg_mesh_set_header": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_dbl), c_dbl, c_dbl, c_vp]),
+    "slg_mesh_grid": (c_i32, [c_vp, c_i64, c_i32, c_dbl, c_vp, c_i64, c_vp]),
+    "slg_mesh_splat": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "slg_mesh_divergence": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "slg_mesh_solve": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp]),
+    "slg_mesh_sample": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "slg_mesh_iso": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "slg_mesh_count": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp]),
+    "slg_mesh_emit": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "slg_mesh_quantile": (c_i32, [c_vp, c_i64, c_dbl, c_vp, c_i64, c_vp]),
+    "slg_mesh_remove": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "slg_mesh_triangle_normals": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "slg_mesh_stl_pack": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
 }
+MESH_HDR_BYTES, MESH_MAX_DEPTH = 256, 10         # SLG_MESH_HDR_BYTES; kMaxDepth of csrc/cloud_mesh.hip
+# SLG_MESH_WS_*: the stages of slg_mesh_ws_bytes
+(MESH_WS_GRID, MESH_WS_SPLAT, MESH_WS_SOLVE, MESH_WS_ISO, MESH_WS_EXTRACT, MESH_WS_QUANTILE, MESH_WS_REMOVE,
+ MESH_WS_ALL) = range(8)
 ORIENT_MAX_K, ORIENT_STATS_LEN = 128, 128        # SLG_ORIENT_MAX_K, SLG_ORIENT_STATS_LEN
 # SLG_ORIENT_STAT_*: indices into the stats of slg_emst / slg_orient_tangent
 (ORIENT_STAT_EMST_ROUNDS, ORIENT_STAT_TREE_ROUNDS, ORIENT_STAT_LIST_FAR, ORIENT_STAT_WALKED, ORIENT_STAT_FAR,

@@ -1,7 +1,7 @@
 // cloud_grid.hip -- the sparse uniform grid of the device cloud steps (cloud_grid.h says what it
 // is): workspace layout and binding, bounding box, cell size, grid build, and the order-preserving
-// select that follows the filters.  rocPRIM is included here only, so the sort and the scans are
-// instantiated once; the other cloud files scan through scan_u32().
+// select that follows the filters.  rocPRIM's 64-bit-key sort and 32-bit scans are instantiated
+// here only; the other cloud files scan through scan_u32() (cloud_mesh.hip has its own types).
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/functional.hpp>

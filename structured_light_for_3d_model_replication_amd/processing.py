@@ -662,6 +662,134 @@ class ProcessingLogic:
             print(f"[360 Mesh] Normals point cloud saved ({len(pcd)} points).")
         return pcd if return_obj else None
 
+    @staticmethod
+    def _check_grid_poisson(depth, width=0.0, linear_fit=False):
+        """What the dense grid takes of ``create_from_point_cloud_poisson``'s arguments."""
+        from . import mesh as MS
+        depth = int(depth)
+        if depth > 16:
+            raise ValueError(f"Depth {depth} is too high! Maximum recommended is 12-14. >16 will freeze your PC.")
+        if float(width) != 0.0 or linear_fit:
+            raise ValueError("width != 0 and linear_fit=True are not implemented on the dense grid")
+        return MS.check_depth(depth)
+
+    @staticmethod
+    def _write_mesh(mesh, output_path, tag):
+        from . import mesh as MS
+        MS.compute_triangle_normals(mesh)
+        MS.write_stl(output_path, mesh)
+        print(f"[{tag}] Saved STL to {output_path}")
+
+    @staticmethod
+    def reconstruct_stl(input_path, output_path, mode="watertight", params=None, centroid_orient=True,
+                        consistency_pass=False, consistency_k=30, meshlab_params=None, save_normals_path=None):
+        """``server/processing.py:632-787`` on the device: normals (estimated at radius 10 / 30
+        when the file has none), the centroid or tangent-plane orientation, the optional consistency
+        pass, then ``mesh.poisson_grid`` at ``params["depth"]`` (default 10), the 0.02 density
+        quantile trim and a binary STL.  The mesher is the dense grid's, so a depth
+        above 10 raises ``ValueError``; ``mode="surface"`` (ball pivoting) raises
+        ``NotImplementedError``: it stays in the reference.  The MeshLab step is restated literally."""
+        from . import cloud as CL
+        from . import mesh as MS
+        if not os.path.exists(input_path):
+            raise FileNotFoundError(f"Input file not found: {input_path}")
+        params = params or {}
+        if mode == "watertight":
+            depth = ProcessingLogic._check_grid_poisson(params.get("depth", 10))
+            MS.check_stl_path(output_path)
+        elif mode == "surface":
+            raise NotImplementedError("mode='surface' (ball pivoting) is a sequential front propagation and stays in the "
+                                      "reference (server/processing.py:711-728)")
+        else:
+            raise ValueError(f"Unknown mode: {mode}")
+        print(f"[Recon] Loading {input_path}...")
+        pcd = CL.PointCloud.from_file(input_path)
+        if not pcd.has_points():
+            raise ValueError("Point cloud is empty.")
+        if not pcd.has_normals():
+            print("[Recon] Estimating normals...")
+            pcd = CL.estimate_normals(pcd, 10, 30)
+        if centroid_orient:
+            pcd = CL.orient_normals_towards(pcd, CL.centroid(pcd), outward=True)
+            print("[Recon] Centroid-based outward orientation applied.")
+        else:
+            print("[Recon] Using tangent-plane graph consistency for normal orientation...")
+            pcd = CL.orient_normals_consistent_tangent_plane(pcd, 100)
+            print("[Recon] Graph orientation applied.")
+        if consistency_pass:
+            k = int(consistency_k) if consistency_k > 0 else 30
+            print(f"[Recon] Consistency pass: orient_normals_consistent_tangent_plane(k={k})...")
+            pcd = CL.orient_normals_consistent_tangent_plane(pcd, k)
+            print("[Recon] Consistency pass applied.")
+        if save_normals_path:
+            print(f"[Recon] Saving normals point cloud to {save_normals_path}...")
+            pcd.save(save_normals_path)
+            print(f"[Recon] Normals point cloud saved ({len(pcd)} points).")
+        print(f"[Recon] Poisson Reconstruction (depth={depth})...")
+        mesh = MS.poisson_grid(pcd, depth=depth)
+        if len(mesh.vertices):
+            mesh = MS.remove_vertices_by_mask(mesh, mesh.densities < MS.quantile(mesh.densities, 0.02))
+        if len(mesh.vertices) == 0:
+            raise ValueError("Generated mesh is empty.")
+        print("[Recon] Computing normals and saving...")
+        ProcessingLogic._write_mesh(mesh, output_path, "Recon")
+        if meshlab_params and meshlab_params.get("enabled"):
+            print("[MeshLab] Starting post-processing...")
+            try:
+                import pymeshlab
+            except ImportError:
+                raise ImportError(
+                    "pymeshlab is not installed. Run: pip install pymeshlab\n"
+                    "The STL has already been saved using Open3D only (without MeshLab improvements)."
+                )
+            ms = pymeshlab.MeshSet()
+            ms.load_new_mesh(output_path)
+            smooth_type = str(meshlab_params.get("smooth_type", "taubin"))
+            smooth_iters = int(meshlab_params.get("smooth_iters", 10))
+            if smooth_type == "laplacian":
+                ms.apply_coord_laplacian_smoothing(stepsmoothnum=smooth_iters)
+            else:
+                ms.apply_coord_taubin_smoothing(stepsmoothnum=smooth_iters)
+            if meshlab_params.get("close_holes"):
+                ms.meshing_close_holes(maxholesize=int(meshlab_params.get("close_max_size", 30)))
+            if meshlab_params.get("simplify"):
+                ms.meshing_decimation_quadric_edge_collapse(targetfacenum=int(meshlab_params.get("target_faces", 50000)))
+            ms.save_current_mesh(output_path)
+            final = ms.current_mesh()
+            print(f"[MeshLab] Post-processing complete. Final: {final.vertex_number()} vertices, "
+                  f"{final.face_number()} faces. Saved to {output_path}")
+
+    @staticmethod
+    def mesh_360(input_path, output_path, depth=10, density_trim=0.01, orientation_mode="tangent", width=0.0,
+                 scale=1.1, linear_fit=False, n_threads=-1, normal_radius=0.1, normal_max_nn=30,
+                 save_normals_path=None):
+        """``server/processing.py:790-860`` on the device: :meth:`estimate_oriented_normals`
+        (``"radial"``, or the tangent-plane orientation with its fall-back for any other mode, as
+        the reference's ``else``), ``mesh.poisson_grid(depth, scale)``, the ``density_trim`` quantile
+        trim when positive, and a binary STL.  ``width != 0`` and ``linear_fit=True`` raise
+        ``ValueError`` (not implemented on the grid), as does a depth above 10; ``n_threads`` is
+        ignored."""
+        from . import mesh as MS
+        if not os.path.exists(input_path):
+            raise FileNotFoundError(f"Input file not found: {input_path}")
+        depth = ProcessingLogic._check_grid_poisson(depth, width, linear_fit)
+        if not (float(scale) >= 1.0):
+            raise ValueError(f"scale must be >= 1 on the dense grid, not {scale}")
+        MS.check_stl_path(output_path)
+        print(f"[360 Mesh] Loading {input_path}...")
+        pcd = ProcessingLogic.estimate_oriented_normals(
+            input_path, save_normals_path, normal_radius, normal_max_nn, outward=True, return_obj=True,
+            orientation_mode="radial" if orientation_mode == "radial" else "tangent")
+        print(f"[360 Mesh] Poisson Reconstruction (depth={depth}, width={width}, scale={scale}, linear={linear_fit}, "
+              f"threads={n_threads})...")
+        mesh = MS.poisson_grid(pcd, depth=depth, scale=scale)
+        if density_trim > 0.0 and len(mesh.vertices):
+            print(f"[360 Mesh] Trimming low density vertices (threshold={density_trim})...")
+            mesh = MS.remove_vertices_by_mask(mesh, mesh.densities < MS.quantile(mesh.densities, density_trim))
+        else:
+            print("[360 Mesh] Density trim is 0.0 -> Keeping watertight result.")
+        ProcessingLogic._write_mesh(mesh, output_path, "360 Mesh")
+
 
 def batch_views() -> int:
     """Views per batched launch in batch mode: ``SLG_BATCH_VIEWS`` (1..16), default 1.  The file

@@ -62,6 +62,14 @@ ties: it runs on the view voxel-down-sampled to at most ``--orient-cpu-points`` 
 recorded), the device runs on that cloud too, and the tool asserts that the trees agree.
 ``--orient-only`` leaves every other step out.
 
+``--mesh DEPTH`` adds the watertight mesher: normals of the view at radius 5.0 / 30
+oriented outward from the centroid, then ``mesh.poisson_grid(depth=DEPTH)`` with HIP events around
+its stages, the 0.02 quantile trim, the triangle normals and the STL records.  It reports the mean
+per-stage times, ``V``, ``T``, the cycles, the workspace, and the solve's rate against a byte model
+(per cycle and node of the finest level 4 sweeps and a residual at 24 B, 8 B for the restriction and
+16 B for the prolongation, times 8/7 for the coarser levels).  ``--mesh-only`` leaves every other
+step out.
+
 Prints one JSON line.
 """
 from __future__ import annotations
@@ -107,6 +115,8 @@ def main():
                     help="with --orient: the normal estimation before it")
     ap.add_argument("--orient-cpu-points", type=int, default=20000, help="with --orient: the size the host side runs at")
     ap.add_argument("--orient-only", action="store_true", help="with --orient: leave every other step out")
+    ap.add_argument("--mesh", type=int, metavar="DEPTH", help="also time the watertight mesher at this depth")
+    ap.add_argument("--mesh-only", action="store_true", help="with --mesh: leave every other step out")
     args = ap.parse_args()
 
     import numpy as np
@@ -139,6 +149,43 @@ def main():
 
     res = {"tool": "cloud_filter_bench", "points": n, "row_mode": args.row_mode, "cam": [W, H],
            "steps": args.steps, "device": torch.cuda.get_device_name(0)}
+    if args.mesh:
+        from structured_light_for_3d_model_replication_amd import mesh as MS
+        depth = int(args.mesh)
+        src = CL.orient_normals_towards(CL.estimate_normals(pc, 5.0, 30), CL.centroid(pc), outward=True)
+        stages = []
+
+        def run():
+            t = {}
+            m = MS.poisson_grid(src, depth=depth, timings=t)
+            stages.append(t)
+            return m
+
+        mesh, ms = timed(run)
+        print(f"[device] poisson_grid done {ms}", file=sys.stderr, flush=True)
+        stages = stages[args.warmup:]
+        mean = lambda v: sum(v) / len(v)
+        stage_ms = {k: mean([t[k] for t in stages]) for k in stages[0]}
+        thr, ms_q = timed(lambda: MS.quantile(mesh.densities, 0.02))
+        trimmed, ms_rm = timed(lambda: MS.remove_vertices_by_mask(mesh, mesh.densities < thr))
+        _, ms_nrm = timed(lambda: MS.compute_triangle_normals(trimmed))
+        _, ms_stl = timed(lambda: MS.stl_records(trimmed))
+        nodes = ((1 << depth) + 1) ** 3
+        model = MS.DEFAULT_CYCLES * nodes * (4 * 24 + 24 + 8 + 16) * 8 / 7
+        res["mesh"] = {
+            "depth": depth, "points": n, "cycles": MS.DEFAULT_CYCLES, "normal_radius": 5.0, "normal_max_nn": 30,
+            "device_ms": ms, **{"stage_" + k: v for k, v in stage_ms.items()},
+            "stage_quantile_ms": mean(ms_q), "stage_remove_ms": mean(ms_rm), "stage_triangle_normals_ms": mean(ms_nrm),
+            "stage_stl_records_ms": mean(ms_stl),
+            "what_is_timed": "device_ms: poisson_grid with its allocations and the header's read-back; stage_*: HIP events",
+            "vertices": len(mesh.vertices), "triangles": len(mesh.triangles),
+            "vertices_after_trim": len(trimmed.vertices), "triangles_after_trim": len(trimmed.triangles),
+            "workspace_bytes": MS.workspace_bytes(depth, n),
+            "solve_model_bytes": model, "solve_model_tb_per_s": model / (stage_ms["solve_ms"] * 1e-3) / 1e12}
+        del mesh, trimmed
+        if args.mesh_only:
+            print(json.dumps(res))
+            return
     if args.orient:
         import orient_ref as OR
         NAT = CL.N
