@@ -1219,9 +1219,12 @@ __device__ inline int bgr_slot(int m) { return m + (m >> SLG_BGR_PAD); }
 #ifndef SLG_X64_KEEP_T
 #define SLG_X64_KEEP_T 1                   // f64 XYZ, pinhole rays: t in registers, ray recomputed in phase D
 #endif
-// Phase B of main3 for rounds [i, i + G) (item m = tid + 256 * round), FAST path: the G items'
-// loads and fp64 chains are independent, so their plane gathers are in flight together.
+// Phase B of main3 for rounds [i, i + G) (item m = tid + kTileBlock * round), FAST path: the G
+// items' loads and fp64 chains are independent, so their plane gathers are in flight together.
 // tri_rounds: i is a compile-time multiple of G (the unrolled group loop); tri_rounds_at: any i.
+// This is the grouped schedule (SLG_TRI_GROUP): the instances without static schedules run it
+// (row_mode 2 with f32 XYZ, or every instance of a -DSLG_TRI_STATIC=0 build); the others take
+// tri_rounds_static below.
 template <int G, int ROW_MODE, int RAYS, typename XT, int NS, int kIt, int NP = 0, int NC = 3>
 __device__ inline void tri_rounds_at(const MainParams& p, int i, int n_items, const uint2* s_item,
                                      XT (&pts)[NS][kIt][NC], uint64_t (&km)[NS][kIt]) {
@@ -1273,6 +1276,104 @@ template <int G, int ROW_MODE, int RAYS, typename XT, int NS, int kIt, int NP = 
 __device__ inline void tri_rounds(const MainParams& p, int i, int n_items, const uint2* s_item,
                                   XT (&pts)[NS][kIt][NC], uint64_t (&km)[NS][kIt]) {
   tri_rounds_at<G, ROW_MODE, RAYS, XT, NS, kIt, NP, NC>(p, i, n_items, s_item, pts, km);
+}
+
+// Phase B of main3 for rounds [I0, I0 + R), both compile-time (a tile of R <= SLG_TRI_STATIC
+// rounds: I0 = 0; a longer one: rounds 0..3, then the rest), FAST path: ONE gather round trip.
+// tri_rounds_at's groups are serial -- the next group's gathers leave only after the previous
+// combine -- so a tile of 5 or 6 rounds (86 % of the C2 views' tiles) paid two loaded L2 round
+// trips, the second for one or two rounds.  Here every round index is a compile-time constant
+// (the caller dispatches on the block-uniform round count), so there are no r == i + h select
+// chains, and the schedule is:
+//   1. the R codes from LDS (one address, immediate round offsets), then item by item its
+//      column plane's and its row plane's gathers, the code dead once they are out (8 VGPRs a
+//      plane: at most 96 VGPRs of planes in flight at R = 6, when phase A's frame registers
+//      are dead);
+//   2. the items consumed in issue order, singly while SLG_TRI_WIDE or more other items'
+//      planes are held, then SLG_TRI_ILP at a time: each item's pixel is read from LDS one
+//      item ahead and its ray computed just before its combine, so at most SLG_TRI_ILP rays
+//      are live while the later planes land (the compiler's vmcnt waits count down with the
+//      issue order), and every consumed item frees 16 VGPRs of planes for 3 (f32), 6 (f64)
+//      or 2 (keep-t) of point.
+// The scheduling barriers keep the max-ilp scheduler from hoisting the later rays over the
+// earlier combines (which would hold R rays beside R planes).  Per item the fp64 operations,
+// their order, the ballots and the ranks are tri_rounds_at's: the same bits.
+// Register budget (4 waves per SIMD: 128 VGPRs): the f32 two-axis instances sit at 128 and the
+// f64 keep-t ones at 126, none with scratch.  What had to go to get there: the six rounds' (u, v)
+// and in-range flags held from the start (re-read / recomputed per item), one LDS address per
+// round (item_slot is linear in the round), and an out-of-line call (forced inline: MainParams
+// lived in scratch otherwise).  A plane spilled while the gathers are issued costs a vmcnt wait
+// between them, i.e. the second round trip back.  The profiling instance, which carries the
+// phase stamps too, did not fit (32 bytes of scratch, and slower as a whole for it): it defers
+// the last two items' row gathers (LATE) and has none.
+#ifndef SLG_TRI_STATIC
+#define SLG_TRI_STATIC 6                   // tiles of up to this many rounds take tri_rounds_static (0: none)
+#endif
+#ifndef SLG_TRI_ILP
+#define SLG_TRI_ILP 2                      // items whose ray + combine chains are interleaved
+#endif
+#ifndef SLG_TRI_WIDE
+#define SLG_TRI_WIDE 4                     // ... once fewer than this many other items' planes are held
+#endif
+template <int I0, int R, int ROW_MODE, int RAYS, typename XT, int NS, int kIt, int NP = 0, int NC = 3, int LATE = 0>
+__device__ __forceinline__ void tri_rounds_static(const MainParams& p, int n_items, const uint2* s_item,
+                                         XT (&pts)[NS][kIt][NC], uint64_t (&km)[NS][kIt]) {
+  static_assert(I0 >= 0 && R >= 1 && I0 + R <= kIt, "rounds of one tile");
+  const int tid = threadIdx.x;
+  TriPlanes pl[R];
+  uint32_t codes[R];
+  // LATE (the profiling instance, whose phase stamps take the registers): the last LATE items'
+  // row planes, needed last of all, are gathered once item 0 has freed its planes
+  constexpr int kLate = R >= 6 ? LATE : 0;
+  // m < kTilePx: items past n_items are read and masked (code 0, pixel (0, 0), kept by no stream)
+  const int m0 = tid + kTileBlock * I0;             // item of round I0 + h: m0 + kTileBlock * h
+  // ... in slot sl0[kRound * h]: one LDS address and immediate offsets, not one address per round
+  static_assert(kTileBlock % (1 << SLG_ITEM_PAD) == 0, "item_slot is linear in the round");
+  constexpr int kRound = kTileBlock + (kTileBlock >> SLG_ITEM_PAD);
+  const uint2* sl0 = s_item + item_slot(m0);
+#pragma unroll
+  for (int h = 0; h < R; ++h) codes[h] = sl0[kRound * h].x;
+#pragma unroll
+  for (int h = 0; h < R; ++h) {                    // an item's code is dead once its gathers are out
+    const uint32_t code = m0 + kTileBlock * h < n_items ? codes[h] : 0u;
+    tri_planes_col<NP>(p, code, pl[h].pc01, pl[h].pc23);
+    if (h < R - kLate) tri_planes_row<ROW_MODE, NP>(p, code, pl[h].pr01, pl[h].pr23);
+    else codes[h] = code;
+  }
+  // the pixel of an item is read from LDS one item ahead of its ray, not held for all R
+  uint32_t uv_next = sl0[0].y;
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int h = 0; h < R; ++h) {
+    {
+      const bool in = m0 + kTileBlock * h < n_items;
+      const uint32_t uv = in ? uv_next : 0u;
+      if (h + 1 < R) uv_next = sl0[kRound * (h + 1)].y;
+      double r0, r1, r2;
+      tri_ray<RAYS, true>(p, int(uv & 0xffffu), int(uv >> 16), r0, r1, r2);
+      const TriOut o = tri_combine<ROW_MODE, true, NP>(p, pl[h], r0, r1, r2);
+      const uint32_t keep = in ? o.keep : 0u;
+      if constexpr (NC == 1) {                     // the ray parameters only (x64_keep_t)
+        pts[0][I0 + h][0] = o.t;
+        if constexpr (ROW_MODE == 2) pts[NS - 1][I0 + h][0] = o.tr;
+      } else {
+        pts[0][I0 + h][0] = XT(o.x); pts[0][I0 + h][1] = XT(o.y); pts[0][I0 + h][2] = XT(o.z);
+        if constexpr (ROW_MODE == 2) {
+          pts[NS - 1][I0 + h][0] = XT(o.rx); pts[NS - 1][I0 + h][1] = XT(o.ry); pts[NS - 1][I0 + h][2] = XT(o.rz);
+        }
+      }
+#pragma unroll
+      for (int s = 0; s < NS; ++s) km[s][I0 + h] = __ballot((keep >> s) & 1u);
+    }
+    if (kLate > 0 && h == 0) {
+#pragma unroll
+      for (int g = R - kLate; g < R; ++g) tri_planes_row<ROW_MODE, NP>(p, codes[g], pl[g].pr01, pl[g].pr23);
+    }
+    // a group ends here: items go singly while SLG_TRI_WIDE or more others' planes are still
+    // held, then SLG_TRI_ILP at a time (counted from the last item)
+    const int left = R - 1 - h;
+    if (left >= SLG_TRI_WIDE || left % SLG_TRI_ILP == 0) __builtin_amdgcn_sched_barrier(0);
+  }
 }
 
 // PROF: the profiling instance (SLG_DBG set): honours the ablation bits of MainParams::dbg and
@@ -1330,11 +1431,10 @@ __global__ __launch_bounds__(kTileBlock, ROW_MODE == 2 && XYZ64 ? 2 : SLG_M3_WAV
   // instance into VGPR spills once the production decode reached the register limit
   __shared__ uint32_t s_rec[8];
   if (prof && tid == 0) s_rec[7] = uint32_t(t_phase);                // start time (low 32 bits)
-  uint32_t polls = 0, naps = 0;
   auto stamp = [&](int k) {
-    if (prof && tid == 0) {
+    if (prof) {                                      // every lane keeps the time: a scalar, no VGPR pair
       const uint64_t t = __builtin_amdgcn_s_memrealtime();
-      s_rec[k] = uint32_t(t - t_phase);
+      if (tid == 0) s_rec[k] = uint32_t(t - t_phase);
       t_phase = t;
     }
   };
@@ -1411,22 +1511,55 @@ __global__ __launch_bounds__(kTileBlock, ROW_MODE == 2 && XYZ64 ? 2 : SLG_M3_WAV
   // recomputes the ray from the item's (u, v): the same code on the same inputs, the same bits.
   constexpr bool KT = XYZ64 && RAYS == SLG_RAYS_PINHOLE && SLG_X64_KEEP_T;
   constexpr int NC = KT ? 1 : 3;
+  // the static round schedules (tri_rounds_static), but for row_mode 2 with f32 XYZ: two streams
+  // of points at 128 VGPRs already spill under the grouped schedule, which that instance keeps
+  constexpr int kStatic = (ROW_MODE == 2 && !XYZ64) ? 0 : SLG_TRI_STATIC;
   XT pts[NS][kIt][NC];
   uint64_t km[NS][kIt];
-  // full groups, then a pair, then a single round: the tail takes at most 3 rounds, so groups
-  // of 1, 2 or 4 (8 left rounds 4..7 of a tile uncomputed: wrong counts, caught by bench verify)
+  // the grouped schedule: full groups, then a pair, then a single round: the tail takes at most
+  // 3 rounds, so groups of 1, 2 or 4 (8 left rounds 4..7 of a tile uncomputed: wrong counts,
+  // caught by bench verify)
   static_assert(kIt % SLG_TRI_GROUP == 0 && (SLG_TRI_GROUP == 1 || SLG_TRI_GROUP == 2 || SLG_TRI_GROUP == 4),
                 "grouped rounds");
   const bool trivial = PROF && (p.dbg & 2);          // ablation: no triangulation arithmetic
   if (p.rays_fast && !trivial) {
     // Several rounds per step: independent straight-line fp64 chains per lane whose plane
     // gathers (L2, high latency under the streaming load) are all in flight together.  The
-    // tile's round count is block-uniform: full groups of SLG_TRI_GROUP rounds, then a pair,
-    // then a single round, so no empty round is computed.
+    // tile's round count is block-uniform, so no empty round is computed: one straight-line
+    // schedule per round count (tri_rounds_static), or, where kStatic is 0, full groups of
+    // SLG_TRI_GROUP rounds, then a pair, then a single round.
     const int rounds = (n_items + kB - 1) / kB;
     int i = 0;
     auto all_rounds = [&](auto np) {
       constexpr int NP = decltype(np)::value;
+      // static schedules: the straight-line instance of the tile's round count -- up to
+      // SLG_TRI_STATIC rounds every gather in one round trip, longer tiles (none in the C2
+      // views) as rounds 0..3, then the rest; SLG_TRI_STATIC 0 keeps the grouped schedule below
+      static_assert(SLG_TRI_STATIC == 0 || (SLG_TRI_STATIC >= 4 && SLG_TRI_STATIC <= 8), "static round schedules");
+      if constexpr (kStatic > 0) {
+        auto stat = [&](auto rc) {
+          constexpr int R = decltype(rc)::value;
+          if constexpr (R <= kStatic && R <= kIt) {
+            tri_rounds_static<0, R, ROW_MODE, RAYS, XT, NS, kIt, NP, NC, PROF ? 2 : 0>(p, n_items, s_item, pts, km);
+          } else if constexpr (R > 4 && R <= kIt) {
+            tri_rounds_static<0, 4, ROW_MODE, RAYS, XT, NS, kIt, NP, NC>(p, n_items, s_item, pts, km);
+            tri_rounds_static<4, R - 4, ROW_MODE, RAYS, XT, NS, kIt, NP, NC>(p, n_items, s_item, pts, km);
+          }
+        };
+        switch (rounds) {
+          case 1: stat(std::integral_constant<int, 1>()); break;
+          case 2: stat(std::integral_constant<int, 2>()); break;
+          case 3: stat(std::integral_constant<int, 3>()); break;
+          case 4: stat(std::integral_constant<int, 4>()); break;
+          case 5: stat(std::integral_constant<int, 5>()); break;
+          case 6: stat(std::integral_constant<int, 6>()); break;
+          case 7: stat(std::integral_constant<int, 7>()); break;
+          case 8: stat(std::integral_constant<int, 8>()); break;
+          default: break;                            // no item: nothing to triangulate
+        }
+        i = rounds;
+        return;
+      }
 #pragma unroll
       for (int g = 0; g + SLG_TRI_GROUP <= kIt; g += SLG_TRI_GROUP)
         if (i + SLG_TRI_GROUP <= rounds) {
@@ -1502,6 +1635,7 @@ __global__ __launch_bounds__(kTileBlock, ROW_MODE == 2 && XYZ64 ? 2 : SLG_M3_WAV
 
   stamp(1);
   // ------------------------------------------------------------ C: tile offset (look-back)
+  uint32_t polls = 0, naps = 0;
   if (wave == 0) {
 #pragma unroll 1
     for (int s = 0; s < NS; ++s) {

@@ -1,0 +1,271 @@
+"""Phase B of the fused kernel picks a straight-line schedule per workgroup from the tile's round
+count (csrc/slgpu.hip ``tri_rounds_static``: 512 items a round, 4096 pixels a tile, so 0..8
+rounds).  These tests reach every schedule, and the in / out-of-range lane of each last round,
+with the smallest input that does: maps given directly (``Reconstructor.triangulate``, no frames
+rendered) on images of one or two tiles, with exactly ``n`` valid pixels per tile for every ``n``
+at a round boundary.
+
+The codes vary per pixel (a random column plane each, some out of range: clamped), a few column
+planes have a zero normal (``|den| <= 1e-6``: dropped), and the row code is the row plane nearest
+to the pixel's column point, moved 60 rows off for one pixel in eleven (the epipolar test drops
+it, so ``keep`` differs from ``in`` across the lanes of a round).
+
+Checked per instance (row_mode 0 / 1 / 2, XYZ f32 / f64, with and without the numerator tables):
+count, order, XYZ and colours against ``oracle.sl_oracle.reconstruct_processing`` on the same maps
+(f64 exact, f32 within XYZ32_RTOL as the other fused-kernel tests), and the two-tile image bitwise
+equal to its two tiles run as one-tile images (the schedule is a per-workgroup choice: a tile's
+points must not depend on its neighbour's round count).  The principal point is dyadic, so
+moving it up by one tile's rows gives the lower tile's one-tile image the same rays bit for bit.
+One two-view fused launch (frames source) whose views differ in rounds per tile closes the file.
+"""
+import numpy as np
+import pytest
+
+from oracle import sl_oracle as O
+
+XYZ32_RTOL = 1e-4          # as tests/test_gpu_instances.py (BASELINE.json north_star)
+W, TILE_ROWS = 128, 32     # 128 x 32 pixels: one 4096-pixel tile
+TILE = W * TILE_ROWS
+PROJ = (1920, 1080)
+# valid pixels per tile: each side of every round boundary the schedules switch at
+N_VALID = [0, 1, 511, 512, 513, 1536, 1537, 2048, 2049, 2560, 2561, 3072, 3073, 3585, 4095, 4096]
+ZERO_COLS, ZERO_ROWS = (5, 777, 1500), (9, 540)      # planes with a zero normal: den == 0
+
+_shared = {}
+
+
+def _calib():
+    """The default rig's tables for a 128 x 64 camera, rays from cam_K (no ray table), a few
+    planes degenerate.  cx = 66.75, cy = 29.0: dyadic, see the module docstring."""
+    if "cal" not in _shared:
+        from structured_light_for_3d_model_replication_amd import synth
+        cal = dict(synth.default_rig(W, 2 * TILE_ROWS, *PROJ).tables())
+        K = np.asarray(cal["cam_K"], np.float64)
+        assert K[0, 2] * 4 == int(K[0, 2] * 4) and K[1, 2] * 4 == int(K[1, 2] * 4)
+        cal["Nc"] = np.zeros((3, 1))
+        for name, zero in (("wPlaneCol", ZERO_COLS), ("wPlaneRow", ZERO_ROWS)):
+            tab = np.array(cal[name], np.float64)
+            assert tab.shape[0] == 4
+            tab[0:3, list(zero)] = 0.0
+            cal[name] = tab
+        _shared["cal"] = cal
+    return _shared["cal"]
+
+
+def _calib_rows(v0):
+    """The calibration of the image that starts at row v0 of the two-tile image."""
+    cal = dict(_calib())
+    K = np.array(cal["cam_K"], np.float64)
+    K[1, 2] -= v0
+    cal["cam_K"] = K
+    return cal
+
+
+def _codes():
+    """(col, row) int32 [64, 128] and texture uint8 [64, 128, 3], fixed seed."""
+    if "codes" not in _shared:
+        cal = _calib()
+        rng = np.random.default_rng(20240607)
+        h = 2 * TILE_ROWS
+        col = rng.integers(0, PROJ[0], (h, W)).astype(np.int32)
+        flat = col.ravel()
+        flat[3::97] = ZERO_COLS[1]
+        flat[50::211] = ZERO_COLS[0]
+        flat[11::389] = -3                            # clamped to plane 0
+        flat[17::401] = 5000                          # clamped to the last plane
+        # the row plane nearest to each pixel's column point (all pixels valid here)
+        valid = np.arange(h * W)
+        rays = O._rays(cal, valid, h, W)
+        Oc = np.asarray(cal["Oc"], np.float64).reshape(3)
+        _, t, _ = O._intersect(O._planes(cal["wPlaneCol"]), col, valid, rays, Oc)
+        Pt = Oc[:, None] + rays * t
+        pr = O._planes(cal["wPlaneRow"])
+        row = np.empty(h * W, np.int32)
+        for a in range(0, h * W, 1024):
+            q = Pt[:, a:a + 1024]
+            d = np.abs(pr[:, 0:1] * q[0] + pr[:, 1:2] * q[1] + pr[:, 2:3] * q[2] + pr[:, 3:4])
+            d[list(ZERO_ROWS)] = np.inf
+            row[a:a + 1024] = np.argmin(d, axis=0)
+        row[4::11] += 60
+        row[29::307] = ZERO_ROWS[0]
+        row[8::503] = -7
+        tex = rng.integers(0, 256, (h, W, 3)).astype(np.uint8)
+        _shared["codes"] = (col, row.reshape(h, W), tex)
+    return _shared["codes"]
+
+
+def _masks():
+    """Two-tile masks: tile 0 has N_VALID[i] valid pixels, tile 1 N_VALID[(i + 5) % 16] (another
+    round count), placed as a prefix of the tile and scattered."""
+    if "masks" not in _shared:
+        rng = np.random.default_rng(7)
+        out = []
+        for scattered in (False, True):
+            for i, n0 in enumerate(N_VALID):
+                m = np.zeros((2, TILE), np.uint8)
+                for t, n in enumerate((n0, N_VALID[(i + 5) % len(N_VALID)])):
+                    m[t, rng.choice(TILE, n, replace=False) if scattered else np.arange(n)] = 1
+                out.append(m.reshape(2 * TILE_ROWS, W))
+        _shared["masks"] = out
+    return _shared["masks"]
+
+
+def _oracle(rm, k):
+    """The oracle's cloud of mask k (computed once per row_mode, shared, read-only)."""
+    key = ("oracle", rm, k)
+    if key not in _shared:
+        col, row, tex = _codes()
+        P, C = O.reconstruct_processing(col, row, _masks()[k], tex, _calib(), row_mode=rm)
+        P.setflags(write=False)
+        _shared[key] = (P, C)
+    return _shared[key]
+
+
+def test_inputs_reach_every_schedule():
+    """No GPU: the masks hold every round count 0..8 with the last round full, one lane short
+    and one lane over, and the codes make every keep decision occur."""
+    rounds = set()
+    for m in _masks():
+        for t in range(2):
+            n = int(m[t * TILE_ROWS:(t + 1) * TILE_ROWS].sum())
+            assert n in N_VALID
+            rounds.add(-(-n // 512))
+    assert rounds == set(range(9))
+    k = len(N_VALID) - 1                                # tile 0 full
+    full = int(_masks()[k].sum())
+    n0 = len(_oracle(0, k)[0])
+    n1 = len(_oracle(1, k)[0])
+    assert 0 < full - n0 < 200                          # a few |den| <= 1e-6
+    assert 0.05 * n0 < n0 - n1 < 0.2 * n0               # the epipolar test drops about 1 in 11
+    assert n1 > 0.8 * full
+
+
+class _Dev:
+    """Device copies of the maps and one engine per image shape, built once per session."""
+
+    def __init__(self):
+        import torch
+        from structured_light_for_3d_model_replication_amd import engine as E
+        self.E, self.torch = E, torch
+        col, row, tex = _codes()
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+        self.col, self.row, self.tex = up(col), up(row), up(tex)
+        self.masks = [up(m) for m in _masks()]
+        self.eng = {h: E.Reconstructor(h, W) for h in (TILE_ROWS, 2 * TILE_ROWS)}
+        self.cal = {}
+
+    def calib(self, v0, h, tables):
+        key = (v0, h, tables)
+        if key not in self.cal:
+            self.cal[key] = self.E.DeviceCalib(_calib_rows(v0), h, W, tables=tables)
+            assert self.cal[key].rays is None           # pinhole rays from cam_K
+        return self.cal[key]
+
+    def run(self, k, v0, h, rm, x64, tables):
+        """Cloud of rows [v0, v0 + h) of mask k as an image of its own: (xyz, bgr, column points)."""
+        sl = slice(v0, v0 + h)
+        flat = lambda t: t[sl].contiguous().reshape(-1)
+        eng = self.eng[h]
+        out = eng.triangulate(flat(self.col), flat(self.row), flat(self.masks[k]), self.tex[sl].contiguous(),
+                              self.calib(v0, h, tables), row_mode=rm, xyz_f64=bool(x64))
+        P, C = (t.cpu().numpy() for t in out.result())
+        nc = eng.column_points() if rm == 2 else len(P)
+        assert eng.error_flags() & 1 == 0
+        return P, C, nc
+
+
+def _dev():
+    if "dev" not in _shared:
+        _shared["dev"] = _Dev()
+    return _shared["dev"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tables", [True, False], ids=["num_pre", "no_tables"])
+@pytest.mark.parametrize("x64", [0, 1], ids=["f32", "f64"])
+@pytest.mark.parametrize("rm", [0, 1, 2])
+def test_every_round_count_matches_oracle_and_its_tiles(rm, x64, tables):
+    import torch
+    if not torch.cuda.is_available():
+        pytest.fail("gpu tests need a ROCm device")
+    d = _dev()
+    for k in range(len(_masks())):
+        P, C, nc = d.run(k, 0, 2 * TILE_ROWS, rm, x64, tables)
+        Po, Co = _oracle(rm, k)
+        assert P.shape == Po.shape, (k, P.shape, Po.shape)
+        assert np.array_equal(C, Co), k
+        if x64:
+            assert np.array_equal(P, Po), (k, float(np.abs(P - Po).max()) if len(P) else 0.0)
+        else:
+            scale = np.maximum(np.abs(Po), 1e-3)
+            assert np.all(np.abs(P.astype(np.float64) - Po) <= XYZ32_RTOL * scale), k
+        # the same tiles as images of their own: the same bits
+        P0, C0, nc0 = d.run(k, 0, TILE_ROWS, rm, x64, tables)
+        P1, C1, nc1 = d.run(k, TILE_ROWS, TILE_ROWS, rm, x64, tables)
+        assert nc == nc0 + nc1, k
+        wantP = np.concatenate([P0[:nc0], P1[:nc1], P0[nc0:], P1[nc1:]])
+        wantC = np.concatenate([C0[:nc0], C1[:nc1], C0[nc0:], C1[nc1:]])
+        assert P.tobytes() == wantP.tobytes(), k
+        assert C.tobytes() == wantC.tobytes(), k
+
+
+def _two_views():
+    """Two small C2 captures of one geometry whose tiles differ in rounds: a rendered view, and
+    the same view with its right half unlit (white = black there: masked out)."""
+    if "views" not in _shared:
+        from structured_light_for_3d_model_replication_amd import synth
+        rig = synth.default_rig(320, 200, *PROJ)
+        v = synth.render_view(rig, 20.0, seed=5, n_present=44)
+        a = [np.asarray(f) for f in v.frames]
+        b = [f.copy() for f in a]
+        b[0][:, 160:] = b[1][:, 160:]
+        kw = dict(n_cols=PROJ[0], n_rows=PROJ[1], n_sets_col=11, n_sets_row=10, thresh_mode="otsu")
+        views = []
+        for fr in (a, b):
+            col, row, mask = O.decode_processing(fr, **kw)
+            views.append((fr, mask, O.reconstruct_processing(col, row, mask, v.texture, rig.tables(), row_mode=1)))
+        _shared["views"] = (rig.tables(), v.texture, views)
+    return _shared["views"]
+
+
+def test_two_views_differ_in_rounds():
+    """No GPU: some tile has another round count in the second view."""
+    _, _, views = _two_views()
+    per_tile = []
+    for _, mask, _ in views:
+        m = np.asarray(mask).ravel() != 0
+        m = np.concatenate([m, np.zeros(-len(m) % TILE, bool)]).reshape(-1, TILE)
+        per_tile.append(-(-m.sum(axis=1) // 512))
+    assert (per_tile[0] != per_tile[1]).sum() >= 3, per_tile
+    assert per_tile[0].max() >= 5
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("x64", [0, 1], ids=["f32", "f64"])
+def test_two_view_launch_with_different_rounds_per_tile(x64):
+    """One fused launch over both views: each view's cloud equals the oracle's (f64 exact) and
+    its own one-view launch bit for bit."""
+    import torch
+    if not torch.cuda.is_available():
+        pytest.fail("gpu tests need a ROCm device")
+    from structured_light_for_3d_model_replication_amd import engine as E
+    cal, tex, views = _two_views()
+    devs = [E.DeviceFrames(fr, tex) for fr, _, _ in views]
+    H, Wd = devs[0].height, devs[0].width
+    dc = E.DeviceCalib(cal, H, Wd)
+    cfg = E.DecodeConfig(PROJ[0], PROJ[1], 11, 10, "otsu")
+    beng = E.BatchReconstructor(H, Wd, 2)
+    clouds = [E.Cloud(H * Wd, 1, bool(x64)) for _ in devs]
+    beng.run(beng.prepare(devs, cfg, dc, clouds, 1))
+    eng = E.Reconstructor(H, Wd)
+    for dev, cloud, (_, _, (Po, Co)) in zip(devs, clouds, views):
+        P, C = cloud.result()
+        one = eng.reconstruct(dev, cfg, dc, row_mode=1, xyz_f64=bool(x64)).result()
+        assert torch.equal(P, one[0]) and torch.equal(C, one[1])
+        P, C = P.cpu().numpy(), C.cpu().numpy()
+        assert len(Po) > 1000 and P.shape == Po.shape
+        assert np.array_equal(C, Co)
+        if x64:
+            assert np.array_equal(P, Po)
+        else:
+            assert np.all(np.abs(P.astype(np.float64) - Po) <= XYZ32_RTOL * np.maximum(np.abs(Po), 1e-3))
