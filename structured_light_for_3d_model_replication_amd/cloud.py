@@ -190,14 +190,21 @@ def as_point_cloud(obj) -> PointCloud:
     raise TypeError(f"cannot make a PointCloud from {type(obj).__name__}")
 
 
+def _nonempty(pc) -> PointCloud:
+    pc = as_point_cloud(pc)
+    if not pc.has_points():
+        raise ValueError("Point cloud is empty.")
+    return pc
+
+
 # ----------------------------------------------------------------------------- filters
 _WS: dict = {}
 
 
-def _workspace(n: int, k: int, device, need=None) -> torch.Tensor:
-    """The device's workspace, grown to ``need`` bytes (``slg_filter_ws_bytes(n, k)`` when not
-    given; a negative size is the call's error code)."""
-    need = int(N.lib().slg_filter_ws_bytes(n, k)) if need is None else int(need)
+def _workspace(device, need) -> torch.Tensor:
+    """The device's workspace, grown to ``need`` bytes (what the step's ``slg_*_ws_bytes`` returned;
+    a negative size is that call's error code)."""
+    need = int(need)
     if need < 0:
         N.check(-need)
     ws = _WS.get(device)
@@ -234,14 +241,27 @@ def far_count(device) -> int:
     return int(_WS[device][8:12].view(torch.int32).item())
 
 
-def _call(fn, xyz: torch.Tensor, k: int, head, outs, stream, what=None) -> None:
-    """What every wrapper of a workspace call shares: the device guard, the workspace,
-    ``fn(*head, ws, ws_bytes, *outs, stream)``, the error, and (with ``what``) the status word."""
-    with torch.cuda.device(xyz.device):
-        ws = _workspace(xyz.shape[0], k, xyz.device)
-        _raise(fn(*head, E._vp(ws), ws.numel(), *(E._vp(o) for o in outs), E._stream(stream)))
+def _filter_ws(xyz: torch.Tensor, k: int):
+    """The sizing call of the steps whose workspace is the grid's alone (for :func:`_call`)."""
+    return lambda: N.lib().slg_filter_ws_bytes(xyz.shape[0], k)
+
+
+def _call(fn, device, need, head, outs, stream, what=None, *, sized=True) -> torch.Tensor:
+    """What every wrapper of a workspace call shares: the device guard, the workspace of ``need()``
+    bytes (the step's own sizing call, made under the guard: rocPRIM's size query runs on the
+    cloud's device), ``fn(*head, ws, ws_bytes, *outs, stream)`` (``ws`` alone with ``sized=False``:
+    ``slg_cloud_select`` takes no size), the error, and (with ``what``) the status word.  Tensors and ``None`` in
+    ``head`` and ``outs`` go as pointers, everything else as it is.  Returns the workspace: a
+    caller whose own read-back comes before the status word passes no ``what`` and checks after."""
+    def arg(a):
+        return E._vp(a) if a is None or isinstance(a, torch.Tensor) else a
+    with torch.cuda.device(device):
+        ws = _workspace(device, need())
+        size = (ws.numel(),) if sized else ()
+        _raise(fn(*map(arg, head), E._vp(ws), *size, *map(arg, outs), E._stream(stream)))
         if what:
             _check_status(ws, what)
+    return ws
 
 
 def radius_mask(xyz: torch.Tensor, nb_points: int, radius: float, stream=None):
@@ -251,8 +271,8 @@ def radius_mask(xyz: torch.Tensor, nb_points: int, radius: float, stream=None):
     n = xyz.shape[0]
     keep = torch.empty(n, dtype=torch.uint8, device=xyz.device)
     counts = torch.empty(n, dtype=torch.int32, device=xyz.device)
-    _call(N.lib().slg_radius_outlier, xyz, 0, (E._vp(xyz), n, float(radius), int(nb_points)), (keep, counts), stream,
-          "radius_outlier")
+    _call(N.lib().slg_radius_outlier, xyz.device, _filter_ws(xyz, 0), (xyz, n, float(radius), int(nb_points)),
+          (keep, counts), stream, "radius_outlier")
     return keep, counts
 
 
@@ -263,8 +283,8 @@ def statistical_mask(xyz: torch.Tensor, nb_neighbors: int, std_ratio: float, str
     keep = torch.empty(n, dtype=torch.uint8, device=xyz.device)
     avg = torch.empty(n, dtype=torch.float64, device=xyz.device)
     stats = torch.empty(3, dtype=torch.float64, device=xyz.device)
-    _call(N.lib().slg_statistical_outlier, xyz, min(int(nb_neighbors), MAX_NEIGHBORS),
-          (E._vp(xyz), n, int(nb_neighbors), float(std_ratio)), (keep, avg, stats), stream, "statistical_outlier")
+    _call(N.lib().slg_statistical_outlier, xyz.device, _filter_ws(xyz, min(int(nb_neighbors), MAX_NEIGHBORS)),
+          (xyz, n, int(nb_neighbors), float(std_ratio)), (keep, avg, stats), stream, "statistical_outlier")
     return keep, avg, stats
 
 
@@ -278,7 +298,8 @@ def dbscan_labels(xyz: torch.Tensor, eps: float, min_points: int, stream=None):
     labels = torch.empty(n, dtype=torch.int32, device=xyz.device)
     keep = torch.empty(n, dtype=torch.uint8, device=xyz.device)
     info = torch.empty(4, dtype=torch.int32, device=xyz.device)
-    _call(N.lib().slg_dbscan, xyz, 0, (E._vp(xyz), n, float(eps), int(min_points)), (labels, keep, info), stream, "dbscan")
+    _call(N.lib().slg_dbscan, xyz.device, _filter_ws(xyz, 0), (xyz, n, float(eps), int(min_points)),
+          (labels, keep, info), stream, "dbscan")
     return labels, keep, info
 
 
@@ -293,14 +314,12 @@ def select(pc: PointCloud, keep: torch.Tensor, stream=None):
     result has no normals."""
     n = len(pc)
     dev = pc.xyz.device
-    with torch.cuda.device(dev):
-        ws = _workspace(n, 0, dev)
-        out = E.Cloud(n, 0, True, dev)
-        index = torch.empty(n, dtype=torch.int64, device=dev)
-        o = out.struct()
-        _raise(N.lib().slg_cloud_select(E._vp(pc.xyz), E._vp(pc.bgr), n, E._vp(keep.contiguous()), ctypes.byref(o),
-                                        E._vp(index), E._vp(ws), E._stream(stream)))
-        P, C = out._launched_on(stream).result()
+    out = E.Cloud(n, 0, True, dev)
+    index = torch.empty(n, dtype=torch.int64, device=dev)
+    o = out.struct()
+    _call(N.lib().slg_cloud_select, dev, _filter_ws(pc.xyz, 0),
+          (pc.xyz, pc.bgr, n, keep.contiguous(), ctypes.byref(o), index), (), stream, sized=False)
+    P, C = out._launched_on(stream).result()
     return PointCloud(P, C), index[:len(P)]
 
 
@@ -308,9 +327,7 @@ def radius_outlier(pc, nb_points: int, radius: float, return_index: bool = False
     """Open3D ``remove_radius_outlier`` + ``select_by_index`` on the device: a new ``PointCloud``
     of the points with more than ``nb_points`` points (itself included) closer than ``radius``.
     Normals are not carried over: the result has none."""
-    pc = as_point_cloud(pc)
-    if not pc.has_points():
-        raise ValueError("Point cloud is empty.")
+    pc = _nonempty(pc)
     keep, _ = radius_mask(pc.xyz, nb_points, radius)
     out, idx = select(pc, keep)
     return (out, idx) if return_index else out
@@ -319,9 +336,7 @@ def radius_outlier(pc, nb_points: int, radius: float, return_index: bool = False
 def statistical_outlier(pc, nb_neighbors: int, std_ratio: float, return_index: bool = False):
     """Open3D ``remove_statistical_outlier`` + ``select_by_index`` on the device
     (``nb_neighbors`` <= 64).  Normals are not carried over: the result has none."""
-    pc = as_point_cloud(pc)
-    if not pc.has_points():
-        raise ValueError("Point cloud is empty.")
+    pc = _nonempty(pc)
     keep, _, _ = statistical_mask(pc.xyz, nb_neighbors, std_ratio)
     out, idx = select(pc, keep)
     return (out, idx) if return_index else out
@@ -333,9 +348,7 @@ def largest_cluster(pc, eps: float, min_points: int, return_index: bool = False)
     input order (the lowest label among equally large ones).  When every point is noise the input
     cloud itself comes back, with indices ``arange(n)``.  Normals are not carried over: a
     selected result has none."""
-    pc = as_point_cloud(pc)
-    if not pc.has_points():
-        raise ValueError("Point cloud is empty.")
+    pc = _nonempty(pc)
     _, keep, info = dbscan_labels(pc.xyz, eps, min_points)
     if int(info[0].item()) == 0:
         return (pc, torch.arange(len(pc), dtype=torch.int64, device=pc.xyz.device)) if return_index else pc
@@ -350,9 +363,7 @@ def voxel_down_sample(pc, voxel_size: float, return_index: bool = False, stream=
     to right in ascending index; colours the exact mean rounded half up; voxels in ascending order
     of their smallest member index.  The result has no normals.  With ``return_index``:
     ``(cloud, first_index int64 [m], count int32 [m])``."""
-    pc = as_point_cloud(pc)
-    if not pc.has_points():
-        raise ValueError("Point cloud is empty.")
+    pc = _nonempty(pc)
     xyz = _check_xyz(pc.xyz)
     n, dev = xyz.shape[0], xyz.device
     oxyz = torch.empty((n, 3), dtype=torch.float64, device=dev)
@@ -360,7 +371,7 @@ def voxel_down_sample(pc, voxel_size: float, return_index: bool = False, stream=
     first = torch.empty(n, dtype=torch.int64, device=dev)
     count = torch.empty(n, dtype=torch.int32, device=dev)
     m = torch.zeros(1, dtype=torch.int64, device=dev)
-    _call(N.lib().slg_voxel_downsample, xyz, 0, (E._vp(xyz), E._vp(pc.bgr), n, float(voxel_size)),
+    _call(N.lib().slg_voxel_downsample, dev, _filter_ws(xyz, 0), (xyz, pc.bgr, n, float(voxel_size)),
           (oxyz, obgr, first, count, m), stream, "voxel_down_sample")
     m = int(m.item())
     out = PointCloud(oxyz[:m], obgr[:m])
@@ -385,30 +396,26 @@ def normal_covariances(xyz: torch.Tensor, radius: float, max_nn: int, stream=Non
     nrm = torch.empty((n, 3), dtype=torch.float64, device=dev)
     cov = torch.empty((n, 6), dtype=torch.float64, device=dev)
     m = torch.empty(n, dtype=torch.int32, device=dev)
-    _call(N.lib().slg_estimate_normals, xyz, 0, (E._vp(xyz), n, float(radius), int(max_nn)), (nrm, cov, m), stream,
-          "estimate_normals")
+    _call(N.lib().slg_estimate_normals, dev, _filter_ws(xyz, 0), (xyz, n, float(radius), int(max_nn)),
+          (nrm, cov, m), stream, "estimate_normals")
     return cov, m, nrm
 
 
 def estimate_normals(pc, radius: float, max_nn: int = 30):
     """Open3D ``estimate_normals(KDTreeSearchParamHybrid(radius, max_nn))`` on the device
     (``3 <= max_nn <= 64``): a ``PointCloud`` sharing ``xyz`` / ``bgr`` with ``normals`` set."""
-    pc = as_point_cloud(pc)
-    if not pc.has_points():
-        raise ValueError("Point cloud is empty.")
+    pc = _nonempty(pc)
     _, _, nrm = normal_covariances(pc.xyz, radius, max_nn)
     return PointCloud(pc.xyz, pc.bgr, normals=nrm)
 
 
 def centroid(pc, stream=None) -> torch.Tensor:
     """Per-axis mean of the points, float64 ``[3]`` on the device (``get_center()``)."""
-    pc = as_point_cloud(pc)
-    if not pc.has_points():
-        raise ValueError("Point cloud is empty.")
+    pc = _nonempty(pc)
     xyz = _check_xyz(pc.xyz)
     n, dev = xyz.shape[0], xyz.device
     out = torch.empty(3, dtype=torch.float64, device=dev)
-    _call(N.lib().slg_cloud_centroid, xyz, 0, (E._vp(xyz), n), (out,), stream)
+    _call(N.lib().slg_cloud_centroid, dev, _filter_ws(xyz, 0), (xyz, n), (out,), stream)
     return out
 
 
@@ -488,9 +495,7 @@ def _dbl16(T: np.ndarray):
 
 def _register(what, source, target, max_correspondence_distance, init, relative_fitness, relative_rmse,
               max_iteration, return_log, need_normals, stream) -> RegistrationResult:
-    source, target = as_point_cloud(source), as_point_cloud(target)
-    if not (source.has_points() and target.has_points()):
-        raise ValueError("Point cloud is empty.")
+    source, target = _nonempty(source), _nonempty(target)
     if need_normals and not target.has_normals():
         raise ValueError(f"{what}: point-to-plane ICP needs target normals (estimate_normals)")
     d, rf, rr, it = float(max_correspondence_distance), float(relative_fitness), float(relative_rmse), int(max_iteration)
@@ -508,15 +513,11 @@ def _register(what, source, target, max_correspondence_distance, init, relative_
     nrm = target.normals.contiguous() if target.has_normals() else None
     ns, nt = src.shape[0], tgt.shape[0]
     L = N.lib()
-    with torch.cuda.device(dev):
-        ws = _workspace(0, 0, dev, need=L.slg_icp_ws_bytes(ns, nt, it))
-        out = torch.zeros(N.ICP_RESULT_LEN + (it + 1) * N.ICP_LOG_STRIDE, dtype=torch.float64, device=dev)
-        corr = torch.empty(ns, dtype=torch.int32, device=dev)
-        _raise(L.slg_icp_point_to_plane(E._vp(src), ns, E._vp(tgt), E._vp(nrm) if nrm is not None else None, nt, d,
-                                        _dbl16(T0), rf, rr, it, E._vp(ws), ws.numel(), E._vp(out),
-                                        E._vp(corr), E._vp(out[N.ICP_RESULT_LEN:]), E._stream(stream)))
-        _check_status(ws, what)
-        host = out.cpu().numpy()                             # the one read-back: result and log
+    out = torch.zeros(N.ICP_RESULT_LEN + (it + 1) * N.ICP_LOG_STRIDE, dtype=torch.float64, device=dev)
+    corr = torch.empty(ns, dtype=torch.int32, device=dev)
+    _call(L.slg_icp_point_to_plane, dev, lambda: L.slg_icp_ws_bytes(ns, nt, it),
+          (src, ns, tgt, nrm, nt, d, _dbl16(T0), rf, rr, it), (out, corr, out[N.ICP_RESULT_LEN:]), stream, what)
+    host = out.cpu().numpy()                                 # the one read-back: result and log
     res = host[:N.ICP_RESULT_LEN]
     iterations = int(res[19])
     log = host[N.ICP_RESULT_LEN:].reshape(it + 1, N.ICP_LOG_STRIDE)[:iterations + 1].copy() if return_log else None
@@ -560,8 +561,8 @@ def transform(pc, T, stream=None) -> PointCloud:
     nrm = pc.normals.contiguous() if pc.has_normals() else None
     onrm = torch.empty_like(nrm) if nrm is not None else None
     with torch.cuda.device(xyz.device):
-        _raise(N.lib().slg_cloud_transform(E._vp(xyz), E._vp(nrm) if nrm is not None else None, n, _dbl16(M),
-                                           E._vp(oxyz), E._vp(onrm) if onrm is not None else None, E._stream(stream)))
+        _raise(N.lib().slg_cloud_transform(E._vp(xyz), E._vp(nrm), n, _dbl16(M), E._vp(oxyz), E._vp(onrm),
+                                           E._stream(stream)))
     return PointCloud(oxyz, pc.bgr, normals=onrm)
 
 
@@ -594,9 +595,7 @@ def fpfh_features(pc, radius: float, max_nn: int = 100, stream=None):
     """``(fpfh float64 [n, 33], spfh float64 [n, 33], m int32 [n])`` on the device: the feature,
     the simplified histogram it is built from, and the hybrid search's neighbour count (the point
     included)."""
-    pc = as_point_cloud(pc)
-    if not pc.has_points():
-        raise ValueError("Point cloud is empty.")
+    pc = _nonempty(pc)
     if not pc.has_normals():
         raise ValueError("compute_fpfh_feature: the cloud has no normals (estimate_normals)")
     xyz = _check_xyz(pc.xyz)
@@ -605,11 +604,9 @@ def fpfh_features(pc, radius: float, max_nn: int = 100, stream=None):
     spfh = torch.empty((n, N.FPFH_DIM), dtype=torch.float64, device=dev)
     m = torch.empty(n, dtype=torch.int32, device=dev)
     L = N.lib()
-    with torch.cuda.device(dev):
-        ws = _workspace(0, 0, dev, need=L.slg_fpfh_ws_bytes(n, int(max_nn)))
-        _raise(L.slg_fpfh(E._vp(xyz), E._vp(pc.normals.contiguous()), n, float(radius), int(max_nn), E._vp(ws), ws.numel(),
-                          E._vp(fpfh), E._vp(spfh), E._vp(m), E._stream(stream)))
-        _check_status(ws, "compute_fpfh_feature")
+    _call(L.slg_fpfh, dev, lambda: L.slg_fpfh_ws_bytes(n, int(max_nn)),
+          (xyz, pc.normals.contiguous(), n, float(radius), int(max_nn)), (fpfh, spfh, m), stream,
+          "compute_fpfh_feature")
     return fpfh, spfh, m
 
 
@@ -636,12 +633,9 @@ def feature_nearest(source_feature: torch.Tensor, target_feature: torch.Tensor, 
     nn_t = torch.empty(nt, dtype=torch.int32, device=dev) if mutual_filter else None
     m = torch.zeros(1, dtype=torch.int64, device=dev)
     L = N.lib()
-    with torch.cuda.device(dev):
-        ws = _workspace(0, 0, dev, need=L.slg_feature_match_ws_bytes(ns, nt))
-        _raise(L.slg_feature_match(E._vp(a), ns, E._vp(b), nt, int(bool(mutual_filter)), E._vp(ws), ws.numel(), E._vp(nn_s),
-                                   E._vp(nn_t) if nn_t is not None else None, E._vp(pairs), E._vp(m), E._stream(stream)))
-        count = int(m.item())
-    return pairs[:count], nn_s, nn_t
+    _call(L.slg_feature_match, dev, lambda: L.slg_feature_match_ws_bytes(ns, nt),
+          (a, ns, b, nt, int(bool(mutual_filter))), (nn_s, nn_t, pairs, m), stream)
+    return pairs[:int(m.item())], nn_s, nn_t
 
 
 def correspondences_from_features(source_feature, target_feature, mutual_filter: bool = False, stream=None) -> torch.Tensor:
@@ -704,26 +698,25 @@ def ransac_batch(source, target, pairs: torch.Tensor, max_correspondence_distanc
     dev = src.device
     ns, nt, count = src.shape[0], tgt.shape[0], int(count)
     pairs = pairs.to(device=dev, dtype=torch.int64).contiguous()
-    sd = int(seed) & 0xFFFFFFFFFFFFFFFF                      # the seed's 64 bits as the int64 the C ABI takes
-    sd = sd - (1 << 64) if sd >> 63 else sd
     L = N.lib()
-    with torch.cuda.device(dev):
-        ws = _workspace(0, 0, dev, need=L.slg_ransac_ws_bytes(ns, nt, max(count, RANSAC_BATCH)))
-        if prepare:
-            _raise(L.slg_ransac_prepare(E._vp(tgt), nt, E._vp(ws), ws.numel(), E._stream(stream)))
-        records = torch.empty((count, N.RANSAC_RECORD_STRIDE), dtype=torch.float64, device=dev)
-        n_eval = torch.zeros(2, dtype=torch.int32, device=dev)
-        trials = torch.empty((count, N.RANSAC_TRIAL_STRIDE), dtype=torch.float64, device=dev) if return_trials else None
-        corr = torch.empty((int(corr_cap), ns), dtype=torch.int32, device=dev) if corr_cap else None
-        _raise(L.slg_ransac_batch(E._vp(src), ns, E._vp(tgt), nt, E._vp(pairs), pairs.shape[0], int(ransac_n),
-                                  float(edge_length), float(max_correspondence_distance), float(confidence),
-                                  sd, int(first_trial), count, E._vp(ws), ws.numel(), int(max_eval), E._vp(records),
-                                  E._vp(n_eval), E._vp(trials) if trials is not None else None,
-                                  E._vp(corr) if corr is not None else None, int(corr_cap), E._stream(stream)))
-        k, consumed = (int(v) for v in n_eval.cpu())
-        _check_status(ws, "registration_ransac_based_on_feature_matching")
-        return (records[:k].cpu().numpy(), trials.cpu().numpy() if trials is not None else None,
-                corr[:min(k, int(corr_cap))] if corr is not None else None, consumed)
+
+    def need():
+        return L.slg_ransac_ws_bytes(ns, nt, max(count, RANSAC_BATCH))
+
+    if prepare:
+        _call(L.slg_ransac_prepare, dev, need, (tgt, nt), (), stream)
+    records = torch.empty((count, N.RANSAC_RECORD_STRIDE), dtype=torch.float64, device=dev)
+    n_eval = torch.zeros(2, dtype=torch.int32, device=dev)
+    trials = torch.empty((count, N.RANSAC_TRIAL_STRIDE), dtype=torch.float64, device=dev) if return_trials else None
+    corr = torch.empty((int(corr_cap), ns), dtype=torch.int32, device=dev) if corr_cap else None
+    ws = _call(L.slg_ransac_batch, dev, need,
+               (src, ns, tgt, nt, pairs, pairs.shape[0], int(ransac_n), float(edge_length),
+                float(max_correspondence_distance), float(confidence), _seed_i64(seed), int(first_trial), count),
+               (int(max_eval), records, n_eval, trials, corr, int(corr_cap)), stream)
+    k, consumed = (int(v) for v in n_eval.cpu())
+    _check_status(ws, "registration_ransac_based_on_feature_matching")
+    return (records[:k].cpu().numpy(), trials.cpu().numpy() if trials is not None else None,
+            corr[:min(k, int(corr_cap))] if corr is not None else None, consumed)
 
 
 def registration_ransac_based_on_feature_matching(source, target, source_feature, target_feature, mutual_filter,
@@ -744,9 +737,7 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
     them in trial order.  With no passing trial the result is the
     identity with fitness 0."""
     what = "registration_ransac_based_on_feature_matching"
-    source, target = as_point_cloud(source), as_point_cloud(target)
-    if not (source.has_points() and target.has_points()):
-        raise ValueError("Point cloud is empty.")
+    source, target = _nonempty(source), _nonempty(target)
     d, e, c, it = float(max_correspondence_distance), float(edge_length), float(confidence), int(max_iteration)
     if not (d > 0.0 and math.isfinite(d)):
         raise ValueError(f"{what}: max_correspondence_distance must be finite and > 0")
@@ -871,13 +862,12 @@ def plane_batch(pc, distance_threshold, first_trial: int, count: int, ransac_n=3
     xyz = _plane_xyz(pc)
     n, dev, count = xyz.shape[0], xyz.device, int(count)
     L = N.lib()
-    with torch.cuda.device(dev):
-        ws = _workspace(0, 0, dev, need=L.slg_plane_ws_bytes(n, max(count, PLANE_BATCH)))
-        records = torch.empty((count, N.PLANE_RECORD_STRIDE), dtype=torch.float64, device=dev)
-        _raise(L.slg_plane_batch(E._vp(xyz), n, float(distance_threshold), int(ransac_n), _seed_i64(seed), int(first_trial),
-                                 count, E._vp(ws), ws.numel(), E._vp(records), E._stream(stream)))
-        host = records.cpu().numpy()
-        _check_status(ws, "segment_plane")
+    records = torch.empty((count, N.PLANE_RECORD_STRIDE), dtype=torch.float64, device=dev)
+    ws = _call(L.slg_plane_batch, dev, lambda: L.slg_plane_ws_bytes(n, max(count, PLANE_BATCH)),
+               (xyz, n, float(distance_threshold), int(ransac_n), _seed_i64(seed), int(first_trial), count),
+               (records,), stream)
+    host = records.cpu().numpy()
+    _check_status(ws, "segment_plane")
     return host
 
 
@@ -888,16 +878,14 @@ def plane_finish(pc, plane, distance_threshold, stream=None):
     n, dev = xyz.shape[0], xyz.device
     pl = np.ascontiguousarray(np.asarray(plane, np.float64).reshape(4))
     L = N.lib()
-    with torch.cuda.device(dev):
-        ws = _workspace(0, 0, dev, need=L.slg_plane_ws_bytes(n, PLANE_BATCH))
-        index = torch.empty(n, dtype=torch.int64, device=dev)
-        count = torch.zeros(1, dtype=torch.int64, device=dev)
-        out = torch.zeros(N.PLANE_SUMS_LEN + 4, dtype=torch.float64, device=dev)
-        _raise(L.slg_plane_finish(E._vp(xyz), n, _dbl16(pl), float(distance_threshold), E._vp(ws), ws.numel(), E._vp(index),
-                                  E._vp(count), E._vp(out), E._vp(out[N.PLANE_SUMS_LEN:]), E._stream(stream)))
-        host = out.cpu().numpy()
-        m = int(count.item())
-        _check_status(ws, "segment_plane")
+    index = torch.empty(n, dtype=torch.int64, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    out = torch.zeros(N.PLANE_SUMS_LEN + 4, dtype=torch.float64, device=dev)
+    ws = _call(L.slg_plane_finish, dev, lambda: L.slg_plane_ws_bytes(n, PLANE_BATCH),
+               (xyz, n, _dbl16(pl), float(distance_threshold)), (index, count, out, out[N.PLANE_SUMS_LEN:]), stream)
+    host = out.cpu().numpy()
+    m = int(count.item())
+    _check_status(ws, "segment_plane")
     return index[:m], host[:N.PLANE_SUMS_LEN].copy(), host[N.PLANE_SUMS_LEN:].copy()
 
 
@@ -911,9 +899,7 @@ def segment_plane(pc, distance_threshold, ransac_n=3, num_iterations=100, probab
     read back and :class:`PlaneChoice` scans them in trial order.  With no valid trial the result
     is the plane ``(0, 0, 0, 0)`` with no inliers.  ``3 <= ransac_n <= 8``."""
     what = "segment_plane"
-    pc = as_point_cloud(pc)
-    if not pc.has_points():
-        raise ValueError("Point cloud is empty.")
+    pc = _nonempty(pc)
     d, rn, it, pr = float(distance_threshold), int(ransac_n), int(num_iterations), float(probability)
     if rn < 3:
         raise ValueError(f"{what}: ransac_n must be >= 3")
@@ -970,10 +956,6 @@ def remove_plane(pc, distance_threshold, ransac_n=3, num_iterations=1000, seed=0
 EMST_LIST_K = 16            # length of the lists euclidean_mst's rounds start from (the tree does not depend on it)
 
 
-def _orient_ws(n: int, k: int, device) -> torch.Tensor:
-    return _workspace(0, 0, device, need=N.lib().slg_orient_ws_bytes(n, k))
-
-
 def _check_k(k, what: str) -> int:
     k = int(k)
     if k < 1:
@@ -992,19 +974,15 @@ def _sorted_edges(edges: torch.Tensor) -> torch.Tensor:
 def knn_lists_raw(pc, k: int, stream=None):
     """``(idx int32 [n, kk], d2 float64 [n, kk])``, ``kk = min(k, n)``, on the device: for every
     point all points in ascending ``(d2, input index)`` order, the point itself included."""
-    pc = as_point_cloud(pc)
-    if not pc.has_points():
-        raise ValueError("Point cloud is empty.")
+    pc = _nonempty(pc)
     k = _check_k(k, "knn_lists")
     xyz = _check_xyz(pc.xyz)
     n, dev = xyz.shape[0], xyz.device
     kk = min(k, n)
     idx = torch.empty((n, kk), dtype=torch.int32, device=dev)
     d2 = torch.empty((n, kk), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        ws = _orient_ws(n, k, dev)
-        _raise(N.lib().slg_knn_lists(E._vp(xyz), n, k, E._vp(ws), ws.numel(), E._vp(idx), E._vp(d2), E._stream(stream)))
-        _check_status(ws, "knn_lists")
+    L = N.lib()
+    _call(L.slg_knn_lists, dev, lambda: L.slg_orient_ws_bytes(n, k), (xyz, n, k), (idx, d2), stream, "knn_lists")
     return idx, d2
 
 
@@ -1033,18 +1011,14 @@ def euclidean_mst(pc, return_stats: bool = False, list_k: int = EMST_LIST_K, str
     """The Euclidean minimum spanning tree under the total edge order ``(d2, a, b)``: int64
     ``[n - 1, 2]`` on the device, rows ``(a, b)`` with ``a < b`` in ascending order.  With
     ``return_stats`` also the int32 ``[ORIENT_STATS_LEN]`` counters of the rounds (host)."""
-    pc = as_point_cloud(pc)
-    if not pc.has_points():
-        raise ValueError("Point cloud is empty.")
+    pc = _nonempty(pc)
     k = _check_k(list_k, "euclidean_mst")
     xyz = _check_xyz(pc.xyz)
     n, dev = xyz.shape[0], xyz.device
     buf = torch.empty((max(n - 1, 1), 2), dtype=torch.int64, device=dev)     # never a NULL buffer
     stats = torch.zeros(N.ORIENT_STATS_LEN, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        ws = _orient_ws(n, k, dev)
-        _raise(N.lib().slg_emst(E._vp(xyz), n, k, E._vp(ws), ws.numel(), E._vp(buf), E._vp(stats), E._stream(stream)))
-        _check_status(ws, "euclidean_mst")
+    L = N.lib()
+    _call(L.slg_emst, dev, lambda: L.slg_orient_ws_bytes(n, k), (xyz, n, k), (buf, stats), stream, "euclidean_mst")
     edges = _sorted_edges(buf[:n - 1])
     return (edges, stats.cpu().numpy()) if return_stats else edges
 
@@ -1056,9 +1030,7 @@ def orient_normals_consistent_tangent_plane(pc, k: int, return_tree: bool = Fals
     128``; a cloud without normals raises ``RuntimeError`` as Open3D does.  With ``return_tree``:
     ``(cloud, tree int64 [n - 1, 2], root int, info)`` with the Riemannian tree's edges in
     ascending ``(a, b)`` order and ``info = {"emst": edges, "stats": int32 counters}``."""
-    pc = as_point_cloud(pc)
-    if not pc.has_points():
-        raise ValueError("Point cloud is empty.")
+    pc = _nonempty(pc)
     if not pc.has_normals():
         raise RuntimeError("orient_normals_consistent_tangent_plane: the cloud has no normals (estimate_normals)")
     k = _check_k(k, "orient_normals_consistent_tangent_plane")
@@ -1070,11 +1042,9 @@ def orient_normals_consistent_tangent_plane(pc, k: int, return_tree: bool = Fals
     tree = torch.empty((n - 1, 2), dtype=torch.int64, device=dev)
     root = torch.zeros(1, dtype=torch.int64, device=dev)
     stats = torch.zeros(N.ORIENT_STATS_LEN, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        ws = _orient_ws(n, k, dev)
-        _raise(N.lib().slg_orient_tangent(E._vp(xyz), E._vp(nrm), n, k, E._vp(ws), ws.numel(), E._vp(out), E._vp(emst),
-                                          E._vp(tree), E._vp(root), E._vp(stats), E._stream(stream)))
-        _check_status(ws, "orient_normals_consistent_tangent_plane")
+    L = N.lib()
+    _call(L.slg_orient_tangent, dev, lambda: L.slg_orient_ws_bytes(n, k), (xyz, nrm, n, k),
+          (out, emst, tree, root, stats), stream, "orient_normals_consistent_tangent_plane")
     res = PointCloud(pc.xyz, pc.bgr, normals=out)
     if not return_tree:
         return res

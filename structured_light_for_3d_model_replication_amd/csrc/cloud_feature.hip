@@ -24,8 +24,6 @@ constexpr int kFarBlocks = 256;        // workgroups of fpfh_far_kernel, each wi
 constexpr int kMatchTile = 128;        // target rows staged in LDS per tile (33 KB)
 constexpr double kPi = 3.14159265358979323846;
 
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct FpfhWs {
   Ws grid;
   double* lst_d;        // [blocks of 64][kk][64]  d2 of the list entries, ascending (d2, index)
@@ -36,17 +34,14 @@ struct FpfhWs {
   double* spfh;         // [n][33], by input index
 };
 
-size_t fpfh_layout(void* base, size_t grid_bytes, int64_t n, int kk, FpfhWs* w) {
-  size_t o = up256(grid_bytes);
-  auto take = [&](size_t bytes) { void* p = (void*)((uintptr_t)base + o); o = up256(o + bytes); return p; };
+void fpfh_layout(Bump& b, int64_t n, int kk, FpfhWs* w) {
   const size_t entries = (size_t)grid_of(n, 64) * kk * 64;
-  w->lst_d = (double*)take(entries * 8);
-  w->lst_i = (uint32_t*)take(entries * 4);
-  w->cnt = (int32_t*)take((size_t)n * 4);
-  w->far_d = (double*)take((size_t)kFarBlocks * kk * 64 * 8);
-  w->far_i = (uint32_t*)take((size_t)kFarBlocks * kk * 64 * 4);
-  w->spfh = (double*)take((size_t)n * kFeat * 8);
-  return o;
+  w->lst_d = b.take<double>(entries);
+  w->lst_i = b.take<uint32_t>(entries);
+  w->cnt = b.take<int32_t>((size_t)n);
+  w->far_d = b.take<double>((size_t)kFarBlocks * kk * 64);
+  w->far_i = b.take<uint32_t>((size_t)kFarBlocks * kk * 64);
+  w->spfh = b.take<double>((size_t)n * kFeat);
 }
 
 // ---------------------------------------------------------------- the rules (one place each)
@@ -88,65 +83,20 @@ __device__ inline double unit_coord_rule(double v) { return 11.0 * (v + 1.0) * 0
 __device__ inline double spfh_increment_rule(int m) { return 100.0 / (double)(m - 1); }
 
 // ---------------------------------------------------------------- neighbour lists
-// One query per thread at sorted position q: the ring walk with the (d2, index) list in global
-// memory, sorted in place.  Queries open after kMaxRing rings go to fpfh_far_kernel.
+// The hybrid search's lists: cloud_grid.h's list kernels with the radius and the count.
 __global__ __launch_bounds__(64)
 void fpfh_lists_kernel(Hdr* hdr, const double* __restrict__ sxyz, const uint32_t* __restrict__ sidx,
                        const uint64_t* __restrict__ ukeys, const uint32_t* __restrict__ ustart, int64_t n, int kk,
                        double r2, double* lst_d, uint32_t* lst_i, int32_t* __restrict__ cnt,
                        uint32_t* __restrict__ far) {
-  if (hdr->status) return;
-  const int64_t q = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  if (q >= n) return;
-  const size_t base = (size_t)blockIdx.x * kk * 64 + threadIdx.x;
-  TopKI tk{lst_d + base, lst_i + base, kk, 0, 0, -1.0, 0u};
-  if (!ring_walk<true>(hdr, sxyz, sidx, ukeys, ustart, q, r2, tk)) {
-    far[atomicAdd(&hdr->n_far, 1)] = (uint32_t)q;
-    return;
-  }
-  tk.sort();
-  cnt[q] = tk.cnt;
+  lists_body<true>(hdr, sxyz, sidx, ukeys, ustart, n, kk, r2, lst_d, lst_i, cnt, far);
 }
 
-// normals_far_kernel's merge with the lists in global scratch: each lane keeps the best kk of its
-// stride of the whole cloud, the wave takes the smallest (d2, index) head kk times, and lane 0
-// writes the merged list into the query's slot.
 __global__ __launch_bounds__(64)
 void fpfh_far_kernel(const Hdr* hdr, const double* __restrict__ sxyz, const uint32_t* __restrict__ sidx, int64_t n,
                      int kk, double r2, double* far_d, uint32_t* far_i, double* lst_d, uint32_t* lst_i,
                      int32_t* __restrict__ cnt, const uint32_t* __restrict__ far) {
-  if (hdr->status) return;
-  const int lane = threadIdx.x;
-  const int nf = hdr->n_far;
-  const size_t scratch = (size_t)blockIdx.x * kk * 64 + lane;
-  for (int f = blockIdx.x; f < nf; f += gridDim.x) {
-    const int64_t q = far[f];
-    const double p[3] = {sxyz[3 * q], sxyz[3 * q + 1], sxyz[3 * q + 2]};
-    TopKI tk{far_d + scratch, far_i + scratch, kk, 0, 0, -1.0, 0u};
-    scan_range<true>(tk, sxyz, sidx, lane, (uint32_t)n, 64, p, r2);
-    tk.sort();
-    const size_t slot = (size_t)(q / 64) * kk * 64 + (size_t)(q % 64);
-    int head = 0, m = 0;
-    for (int r = 0; r < kk; ++r) {
-      const bool have = head < tk.cnt;
-      const double v = have ? tk.lst[head * 64] : kInf;
-      const uint32_t vi = have ? tk.idx[head * 64] : kNone;
-      const double best = wave_min(v);
-      if (best == kInf) break;                 // every list is used up (uniform over the wave)
-      uint32_t bi = v == best ? vi : kNone;
-      for (int s = 32; s > 0; s >>= 1) {
-        const uint32_t other = (uint32_t)__shfl_xor((int)bi, s, 64);
-        bi = other < bi ? other : bi;
-      }
-      if (have && v == best && vi == bi) ++head;
-      if (lane == 0) {
-        lst_d[slot + (size_t)m * 64] = best;
-        lst_i[slot + (size_t)m * 64] = bi;
-      }
-      ++m;
-    }
-    if (lane == 0) cnt[q] = m;
-  }
+  lists_far_body<true>(hdr, sxyz, sidx, n, kk, r2, far_d, far_i, lst_d, lst_i, cnt, far);
 }
 
 // ---------------------------------------------------------------- SPFH and FPFH
@@ -287,12 +237,9 @@ void match_pairs_kernel(const int32_t* __restrict__ nn_s, int64_t ns, const uint
   if (i == ns - 1) *m_out = (int64_t)pos[i] + flags[i];
 }
 
-size_t match_layout(void* base, size_t grid_bytes, int64_t ns, int64_t nt, int32_t** nn_s, int32_t** nn_t) {
-  size_t o = up256(grid_bytes);
-  auto take = [&](size_t bytes) { void* p = (void*)((uintptr_t)base + o); o = up256(o + bytes); return p; };
-  *nn_s = (int32_t*)take((size_t)ns * 4);
-  *nn_t = (int32_t*)take((size_t)nt * 4);
-  return o;
+void match_layout(Bump& b, int64_t ns, int64_t nt, int32_t** nn_s, int32_t** nn_t) {
+  *nn_s = b.take<int32_t>((size_t)ns);
+  *nn_t = b.take<int32_t>((size_t)nt);
 }
 
 }  // namespace
@@ -305,10 +252,8 @@ extern "C" int64_t slg_fpfh_ws_bytes(int64_t n, int32_t max_nn) {
   if (n > kMaxPoints || max_nn > kFpfhMaxK)
     return -(int64_t)slg_internal_fail(SLG_ERR_UNSUPPORTED, "slg_fpfh_ws_bytes: more than 2^30 points or max_nn > %d",
                                        kFpfhMaxK);
-  const int64_t grid_bytes = slg_filter_ws_bytes(n, 0);
-  if (grid_bytes < 0) return grid_bytes;
   FpfhWs w;
-  return (int64_t)fpfh_layout(nullptr, (size_t)grid_bytes, n, (int)(n < max_nn ? n : max_nn), &w);
+  return ext_ws_bytes(n, 0, [&](Bump& b) { fpfh_layout(b, n, (int)(n < max_nn ? n : max_nn), &w); });
 }
 
 extern "C" int32_t slg_fpfh(const double* xyz, const double* normals, int64_t n, double radius, int32_t max_nn,
@@ -318,16 +263,13 @@ extern "C" int32_t slg_fpfh(const double* xyz, const double* normals, int64_t n,
     return slg_internal_fail(SLG_ERR_INVALID, "slg_fpfh: n <= 0, radius not finite and > 0, max_nn < 2 or a NULL buffer "
                                               "(the cloud needs normals)");
   if (max_nn > kFpfhMaxK) return slg_internal_fail(SLG_ERR_UNSUPPORTED, "slg_fpfh: max_nn > %d", kFpfhMaxK);
+  // begin_call's own refusal, kept ahead of the grid's size query (which would name slg_filter_ws_bytes)
+  if (n > kMaxPoints) return slg_internal_fail(SLG_ERR_UNSUPPORTED, "slg_fpfh: more than 2^30 points");
   FpfhWs w;
-  int rc = begin_call("slg_fpfh", n, ws, -1, &w.grid);
-  if (rc) return rc;
-  const int64_t grid_bytes = slg_filter_ws_bytes(n, 0);
-  if (grid_bytes < 0) return (int32_t)-grid_bytes;
   const int kk = (int)(n < max_nn ? n : max_nn);
-  const size_t total = fpfh_layout(ws, (size_t)grid_bytes, n, kk, &w);
-  if (ws_bytes < 0 || (size_t)ws_bytes < total)
-    return slg_internal_fail(SLG_ERR_INVALID, "slg_fpfh: workspace of %lld bytes, slg_fpfh_ws_bytes gives %lld",
-                             (long long)ws_bytes, (long long)total);
+  int rc = begin_ext_call("slg_fpfh", "slg_fpfh_ws_bytes", n, 0, ws, ws_bytes, &w.grid,
+                          [&](Bump& b) { fpfh_layout(b, n, kk, &w); });
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   if ((rc = knn_grid(xyz, n, w.grid, max_nn, st))) return rc;
   const Ws& g = w.grid;
@@ -347,10 +289,8 @@ extern "C" int64_t slg_feature_match_ws_bytes(int64_t n_source, int64_t n_target
     return -(int64_t)slg_internal_fail(SLG_ERR_INVALID, "slg_feature_match_ws_bytes: n_source <= 0 or n_target <= 0");
   if (n_source > kMaxPoints || n_target > kMaxPoints)
     return -(int64_t)slg_internal_fail(SLG_ERR_UNSUPPORTED, "slg_feature_match_ws_bytes: more than 2^30 rows");
-  const int64_t grid_bytes = slg_filter_ws_bytes(n_source, 0);
-  if (grid_bytes < 0) return grid_bytes;
-  int32_t *a, *b;
-  return (int64_t)match_layout(nullptr, (size_t)grid_bytes, n_source, n_target, &a, &b);
+  int32_t *nn_s, *nn_t;
+  return ext_ws_bytes(n_source, 0, [&](Bump& b) { match_layout(b, n_source, n_target, &nn_s, &nn_t); });
 }
 
 extern "C" int32_t slg_feature_match(const double* source_feature, int64_t n_source, const double* target_feature,
@@ -360,16 +300,13 @@ extern "C" int32_t slg_feature_match(const double* source_feature, int64_t n_sou
   if (n_source <= 0 || n_target <= 0 || !source_feature || !target_feature || !pairs_out || !m_out)
     return slg_internal_fail(SLG_ERR_INVALID, "slg_feature_match: n_source <= 0, n_target <= 0 or a NULL buffer");
   if (n_target > kMaxPoints) return slg_internal_fail(SLG_ERR_UNSUPPORTED, "slg_feature_match: more than 2^30 rows");
+  // begin_call's own refusal, kept ahead of the grid's size query (which would name slg_filter_ws_bytes)
+  if (n_source > kMaxPoints) return slg_internal_fail(SLG_ERR_UNSUPPORTED, "slg_feature_match: more than 2^30 points");
   Ws w;
-  int rc = begin_call("slg_feature_match", n_source, ws, -1, &w);
-  if (rc) return rc;
-  const int64_t grid_bytes = slg_filter_ws_bytes(n_source, 0);
-  if (grid_bytes < 0) return (int32_t)-grid_bytes;
   int32_t *nn_s, *nn_t;
-  const size_t total = match_layout(ws, (size_t)grid_bytes, n_source, n_target, &nn_s, &nn_t);
-  if (ws_bytes < 0 || (size_t)ws_bytes < total)
-    return slg_internal_fail(SLG_ERR_INVALID, "slg_feature_match: workspace of %lld bytes, slg_feature_match_ws_bytes gives %lld",
-                             (long long)ws_bytes, (long long)total);
+  int rc = begin_ext_call("slg_feature_match", "slg_feature_match_ws_bytes", n_source, 0, ws, ws_bytes, &w,
+                          [&](Bump& b) { match_layout(b, n_source, n_target, &nn_s, &nn_t); });
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (nn_source_out) nn_s = nn_source_out;
   if (nn_target_out) nn_t = nn_target_out;

@@ -1,10 +1,13 @@
 // cloud_grid.h -- what the device cloud steps share (included, never compiled alone): the
-// workspace header, the sparse uniform grid's device helpers, the two neighbour walks, the top-k
-// lists, and the host functions of cloud_grid.hip.  Users: cloud_filter.hip (radius count,
-// statistical filter), cloud_cluster.hip (DBSCAN), cloud_normals.hip (voxel down-sample, normals),
-// cloud_icp.hip (point-to-plane ICP's correspondence search), cloud_feature.hip (FPFH's neighbour
-// lists), cloud_ransac.hip (the evaluation of a batch of hypotheses), cloud_orient.hip (the kNN
-// lists and the EMST's walks of the tangent-plane orientation).
+// workspace header, the bump allocator every workspace layout is written with, the prologue of a
+// call whose workspace is a grid with an extension behind it, the sparse uniform grid's device
+// helpers, the two neighbour walks, the top-k lists, the wave-wide merge of 64 such lists and the
+// list kernels' bodies built on it, the seeded draw, and the host functions of cloud_grid.hip.
+// Users: cloud_filter.hip (radius count, statistical filter), cloud_cluster.hip (DBSCAN),
+// cloud_normals.hip (voxel down-sample, normals), cloud_icp.hip (point-to-plane ICP's
+// correspondence search), cloud_feature.hip (FPFH's neighbour lists), cloud_ransac.hip (the draws
+// and the evaluation of a batch of hypotheses), cloud_plane.hip (the draws), cloud_orient.hip (the
+// kNN lists and the EMST's walks of the tangent-plane orientation), cloud_mesh.hip (the allocator).
 //
 // The grid: bbox (fixed-order reduction) -> integer cell coordinates floor((p - min) / cell)
 // packed into a 63-bit key (21 bits per axis, x lowest) -> stable radix sort of (key, index) ->
@@ -84,9 +87,52 @@ struct VoxelScratch { uint32_t *head, *place; };
 
 inline int grid_of(int64_t n, int per) { return (int)((n + per - 1) / per); }
 
+// Every workspace layout: regions in order from byte `start` of the workspace at `base`, each a
+// multiple of 256 bytes; off is the total so far.  A null base only sizes.  The grid's layout
+// starts at 0, an extension's at up256(grid bytes), the mesher's behind its header.
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+struct Bump {
+  uintptr_t base;
+  size_t off;
+  Bump(void* ws, size_t start) : base((uintptr_t)ws), off(start) {}
+  template <class T> T* take(size_t count) {
+    T* p = (T*)(base + off);
+    off = up256(off + count * sizeof(T));
+    return p;
+  }
+};
+
 // ---------------------------------------------------------------- host side (cloud_grid.hip)
 // The point cap and the workspace binding every entry point starts with.
 int begin_call(const char* who, int64_t n, void* ws, int64_t ws_bytes, Ws* w);
+
+// The bytes of a grid workspace of (n, k) with the regions layout(Bump&) takes behind it: what an
+// extension's slg_*_ws_bytes returns after its own refusals (the grid's error code, negated, when
+// the grid refuses).
+template <class Layout>
+int64_t ext_ws_bytes(int64_t n, int k, Layout layout) {
+  const int64_t grid_bytes = slg_filter_ws_bytes(n, k);
+  if (grid_bytes < 0) return grid_bytes;
+  Bump b(nullptr, up256((size_t)grid_bytes));
+  layout(b);
+  return (int64_t)b.off;
+}
+// begin_call for such a workspace: the grid's bytes (its own error is passed on, its text already
+// set), the grid bound to the front of ws, layout(Bump&) behind it, and ws_bytes against the
+// total; `sizer` is the slg_*_ws_bytes the text names.
+template <class Layout>
+int begin_ext_call(const char* who, const char* sizer, int64_t n, int k, void* ws, int64_t ws_bytes, Ws* grid,
+                   Layout layout) {
+  const int64_t grid_bytes = slg_filter_ws_bytes(n, k);
+  if (grid_bytes < 0) return (int32_t)-grid_bytes;
+  if (int rc = begin_call(who, n, ws, -1, grid)) return rc;
+  Bump b(ws, up256((size_t)grid_bytes));
+  layout(b);
+  if (ws_bytes < 0 || (size_t)ws_bytes < b.off)
+    return slg_internal_fail(SLG_ERR_INVALID, "%s: workspace of %lld bytes, %s gives %lld", who, (long long)ws_bytes, sizer,
+                             (long long)b.off);
+  return SLG_OK;
+}
 DbscanScratch dbscan_scratch(const Ws& w, int64_t n);
 VoxelScratch voxel_scratch(const Ws& w, int64_t n);
 // Clears the header, folds the box and fixes the cell (bbox_final_kernel says how).
@@ -316,6 +362,34 @@ struct TopKI {
   }
 };
 
+// The wave-wide merge of the 64 sorted per-lane lists of a whole-cloud kernel: kk times, the
+// smallest (d2, index) head over the wave is taken, the lane that holds it advances, and
+// emit(r, d2, index) sees entry r of the merged list (in every lane).  Returns the number taken.
+// With kRadius the lists can be used up before kk are taken (fewer than kk points inside the
+// radius) and the merge ends there; without it the lists hold the best kk <= n of the whole
+// cloud, so they never are, and the test is left out.
+template <bool kRadius, class Emit>
+__device__ inline int wave_merge(const TopKI& tk, int kk, Emit emit) {
+  int head = 0, r = 0;
+  for (; r < kk; ++r) {
+    const bool have = head < tk.cnt;
+    const double v = have ? tk.lst[head * 64] : kInf;
+    const uint32_t vi = have ? tk.idx[head * 64] : kNone;
+    const double best = wave_min(v);
+    if constexpr (kRadius) {
+      if (best == kInf) break;                 // every list is used up (uniform over the wave)
+    }
+    uint32_t bi = v == best ? vi : kNone;
+    for (int s = 32; s > 0; s >>= 1) {
+      const uint32_t other = (uint32_t)__shfl_xor((int)bi, s, 64);
+      bi = other < bi ? other : bi;
+    }
+    if (have && v == best && vi == bi) ++head;
+    emit(r, best, bi);
+  }
+  return r;
+}
+
 // ---------------------------------------------------------------- the ring walk
 // Offers the sorted positions s, s + step, ... below e to the list; with kRadius only those with
 // d2 < r2.
@@ -404,6 +478,83 @@ __device__ inline bool ring_walk(const Hdr* hdr, const double* __restrict__ sxyz
                                  double r2, List& tk) {
   const double p[3] = {sxyz[3 * q], sxyz[3 * q + 1], sxyz[3 * q + 2]};
   return ring_walk_at<kRadius, false>(hdr, sxyz, sidx, ukeys, ustart, p, r2, tk);
+}
+
+// ---------------------------------------------------------------- neighbour lists in global memory
+// What FPFH (cloud_feature.hip, kRadius: the hybrid search) and the tangent-plane orientation
+// (cloud_orient.hip, plain kNN) keep per point: a (d2, index) list sorted ascending, 64 queries to
+// a block of kk x 64 entries (entry j of lane l at j * 64 + l, the layout TopKI walks), and with
+// kRadius the number of entries of the list of sorted position q in cnt (without the radius every
+// list holds kk <= n entries and cnt is not touched: pass null).  Each file has the two kernels
+// that call these bodies.
+//
+// One query per thread (64 to a workgroup) at sorted position q: the ring walk with the list in
+// global memory, sorted in place.  Queries open after kMaxRing rings go to the far list (at most
+// one entry per point: n entries) and lists_far_body.
+template <bool kRadius>
+__device__ inline void lists_body(Hdr* hdr, const double* __restrict__ sxyz, const uint32_t* __restrict__ sidx,
+                                  const uint64_t* __restrict__ ukeys, const uint32_t* __restrict__ ustart, int64_t n,
+                                  int kk, double r2, double* lst_d, uint32_t* lst_i, int32_t* __restrict__ cnt,
+                                  uint32_t* __restrict__ far) {
+  if (hdr->status) return;
+  const int64_t q = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (q >= n) return;
+  const size_t base = (size_t)blockIdx.x * kk * 64 + threadIdx.x;
+  TopKI tk{lst_d + base, lst_i + base, kk, 0, 0, -1.0, 0u};
+  if (!ring_walk<kRadius>(hdr, sxyz, sidx, ukeys, ustart, q, r2, tk)) {
+    far[atomicAdd(&hdr->n_far, 1)] = (uint32_t)q;
+    return;
+  }
+  tk.sort();
+  if constexpr (kRadius) cnt[q] = tk.cnt;
+}
+
+// One wave per far-list query (grid-stride), each workgroup with kk x 64 entries of scratch at
+// far_d / far_i: each lane keeps the best kk of its stride of the whole cloud, wave_merge takes
+// the smallest (d2, index) head kk times, and lane 0 writes the merged list into the query's slot.
+template <bool kRadius>
+__device__ inline void lists_far_body(const Hdr* hdr, const double* __restrict__ sxyz, const uint32_t* __restrict__ sidx,
+                                      int64_t n, int kk, double r2, double* far_d, uint32_t* far_i, double* lst_d,
+                                      uint32_t* lst_i, int32_t* __restrict__ cnt, const uint32_t* __restrict__ far) {
+  if (hdr->status) return;
+  const int lane = threadIdx.x;
+  const int nf = hdr->n_far;
+  const size_t scratch = (size_t)blockIdx.x * kk * 64 + lane;
+  for (int f = blockIdx.x; f < nf; f += gridDim.x) {
+    const int64_t q = far[f];
+    const double p[3] = {sxyz[3 * q], sxyz[3 * q + 1], sxyz[3 * q + 2]};
+    TopKI tk{far_d + scratch, far_i + scratch, kk, 0, 0, -1.0, 0u};
+    scan_range<kRadius>(tk, sxyz, sidx, lane, (uint32_t)n, 64, p, r2);
+    tk.sort();
+    const size_t slot = (size_t)(q / 64) * kk * 64 + (size_t)(q % 64);
+    const int m = wave_merge<kRadius>(tk, kk, [&](int r, double d2, uint32_t i) {
+      if (lane == 0) {
+        lst_d[slot + (size_t)r * 64] = d2;
+        lst_i[slot + (size_t)r * 64] = i;
+      }
+    });
+    if constexpr (kRadius) {
+      if (lane == 0) cnt[q] = m;
+    }
+  }
+}
+
+// ---------------------------------------------------------------- the seeded draw
+// What the registration RANSAC (cloud_ransac.hip) and the plane RANSAC (cloud_plane.hip) draw
+// their samples with; tests/feature_ref.py restates both.
+// The finaliser of SplitMix64 (Steele, Lea, Flood 2014; Stafford's mix 13): integer operations only.
+__device__ inline uint64_t mix64_rule(uint64_t z) {
+  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+  z ^= z >> 27; z *= 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return z;
+}
+// Draw k of trial t, with kStride draws reserved per trial: an index below m from the hash's upper
+// 32 bits by a multiply-high.
+template <int kStride>
+__device__ inline uint32_t draw_rule(uint64_t seed, uint64_t t, uint32_t k, uint32_t m) {
+  const uint64_t h = mix64_rule(mix64_rule(seed + 0x9E3779B97F4A7C15ull) + (t * (uint64_t)kStride + k));
+  return (uint32_t)(((h >> 32) * (uint64_t)m) >> 32);
 }
 
 // ---------------------------------------------------------------- evaluating a transform

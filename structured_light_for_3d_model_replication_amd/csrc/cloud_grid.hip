@@ -12,8 +12,6 @@
 namespace slgcloud {
 
 // ---------------------------------------------------------------- workspace
-static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct U8ToU32 {
   __host__ __device__ uint32_t operator()(uint8_t v) const { return v ? 1u : 0u; }
 };
@@ -38,25 +36,24 @@ static hipError_t temp_bytes_for(int64_t n, size_t* out) {
 // The regions of a workspace for n points at `base`, in order, each a multiple of 256 bytes;
 // *total gets their sum (base may be null when only the size is wanted).
 static Ws make_layout(void* base, int64_t n, size_t temp_bytes, size_t* total) {
-  size_t o = 0;
   const size_t N = (size_t)n;
-  auto take = [&](size_t bytes) { void* p = (void*)((uintptr_t)base + o); o = up256(o + bytes); return p; };
+  Bump b(base, 0);
   Ws w;
-  w.hdr = (Hdr*)take(256);
-  w.keys = (uint64_t*)take(N * 8);
-  w.keys_s = (uint64_t*)take(N * 8);
-  w.idx = (uint32_t*)take(N * 4);
-  w.idx_s = (uint32_t*)take(N * 4);
-  w.sxyz = (double*)take(N * 24);
-  w.pos = (uint32_t*)take(N * 4);
-  w.ukeys = (uint64_t*)take(N * 8);
-  w.ustart = (uint32_t*)take((N + 1) * 4);
-  w.part = (double*)take(((N + kChunk - 1) / kChunk) * 6 * 8);
-  w.avg = (double*)take(N * 8);
-  w.far = (uint32_t*)take(N * 4);
-  w.temp = take(temp_bytes);
+  w.hdr = b.take<Hdr>(1);
+  w.keys = b.take<uint64_t>(N);
+  w.keys_s = b.take<uint64_t>(N);
+  w.idx = b.take<uint32_t>(N);
+  w.idx_s = b.take<uint32_t>(N);
+  w.sxyz = b.take<double>(N * 3);
+  w.pos = b.take<uint32_t>(N);
+  w.ukeys = b.take<uint64_t>(N);
+  w.ustart = b.take<uint32_t>(N + 1);
+  w.part = b.take<double>(((N + kChunk - 1) / kChunk) * 6);
+  w.avg = b.take<double>(N);
+  w.far = b.take<uint32_t>(N);
+  w.temp = b.take<uint8_t>(temp_bytes);
   w.temp_bytes = temp_bytes;
-  *total = o;
+  *total = b.off;
   return w;
 }
 

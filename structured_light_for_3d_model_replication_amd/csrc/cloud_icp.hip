@@ -41,18 +41,13 @@ struct IcpWs {
   double* log;
 };
 
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// The regions behind the filter workspace of grid_bytes bytes; returns the total.
-size_t icp_layout(void* base, size_t grid_bytes, int64_t ns, int32_t max_iteration, IcpWs* w) {
-  size_t o = up256(grid_bytes);
-  auto take = [&](size_t bytes) { void* p = (void*)((uintptr_t)base + o); o = up256(o + bytes); return p; };
-  w->st = (IcpState*)take(256);
-  w->part = (double*)take((size_t)grid_of(ns, kChunk) * kTerms * 8);
-  w->corr = (int32_t*)take((size_t)ns * 4);
-  w->far = (uint32_t*)take((size_t)ns * 4);
-  w->log = (double*)take(((size_t)max_iteration + 1) * kLogStride * 8);
-  return o;
+// The regions behind the target grid's workspace.
+void icp_layout(Bump& b, int64_t ns, int32_t max_iteration, IcpWs* w) {
+  w->st = b.take<IcpState>(1);
+  w->part = b.take<double>((size_t)grid_of(ns, kChunk) * kTerms);
+  w->corr = b.take<int32_t>((size_t)ns);
+  w->far = b.take<uint32_t>((size_t)ns);
+  w->log = b.take<double>(((size_t)max_iteration + 1) * kLogStride);
 }
 
 // ---------------------------------------------------------------- the rules (one place each)
@@ -359,10 +354,8 @@ extern "C" int64_t slg_icp_ws_bytes(int64_t n_source, int64_t n_target, int32_t 
   if (n_source > kMaxPoints || n_target > kMaxPoints || max_iteration > kMaxIterations)
     return -(int64_t)slg_internal_fail(SLG_ERR_UNSUPPORTED, "slg_icp_ws_bytes: more than 2^30 points or max_iteration > %d",
                                        kMaxIterations);
-  const int64_t grid_bytes = slg_filter_ws_bytes(n_target, kIcpGridK);
-  if (grid_bytes < 0) return grid_bytes;
   IcpWs w;
-  return (int64_t)icp_layout(nullptr, (size_t)grid_bytes, n_source, max_iteration, &w);
+  return ext_ws_bytes(n_target, kIcpGridK, [&](Bump& b) { icp_layout(b, n_source, max_iteration, &w); });
 }
 
 extern "C" int32_t slg_icp_point_to_plane(const double* src_xyz, int64_t n_source, const double* tgt_xyz,
@@ -379,15 +372,10 @@ extern "C" int32_t slg_icp_point_to_plane(const double* src_xyz, int64_t n_sourc
   if (n_source > kMaxPoints || max_iteration > kMaxIterations)
     return slg_internal_fail(SLG_ERR_UNSUPPORTED, "slg_icp_point_to_plane: more than 2^30 points or max_iteration > %d",
                              kMaxIterations);
-  const int64_t grid_bytes = slg_filter_ws_bytes(n_target, kIcpGridK);
-  if (grid_bytes < 0) return (int32_t)-grid_bytes;           // its text is already set
   IcpWs w;
-  int rc = begin_call("slg_icp_point_to_plane", n_target, ws, -1, &w.grid);
+  int rc = begin_ext_call("slg_icp_point_to_plane", "slg_icp_ws_bytes", n_target, kIcpGridK, ws, ws_bytes, &w.grid,
+                          [&](Bump& b) { icp_layout(b, n_source, max_iteration, &w); });
   if (rc) return rc;
-  const size_t total = icp_layout(ws, (size_t)grid_bytes, n_source, max_iteration, &w);
-  if (ws_bytes < 0 || (size_t)ws_bytes < total)
-    return slg_internal_fail(SLG_ERR_INVALID, "slg_icp_point_to_plane: workspace of %lld bytes, slg_icp_ws_bytes gives %lld",
-                             (long long)ws_bytes, (long long)total);
   hipStream_t st = (hipStream_t)stream;
   Mat4 T;
   for (int k = 0; k < 16; ++k) T.m[k] = init_T[k];

@@ -20,6 +20,7 @@
 namespace slgmesh {
 
 using slgcloud::block_tree_sum;
+using slgcloud::Bump;
 using slgcloud::grid_of;
 using slgcloud::kChunk;
 
@@ -45,16 +46,7 @@ __device__ constexpr int kEdgeCode[7] = {1, 2, 4, 3, 5, 6, 7};
 __device__ constexpr int kTypeOfCode[8] = {-1, 0, 1, 3, 2, 4, 5, 6};
 
 // ---------------------------------------------------------------- workspace
-struct Bump {           // regions in order, each a multiple of 256 bytes, after the header
-  uintptr_t base;
-  size_t off = SLG_MESH_HDR_BYTES;
-  explicit Bump(void* ws) : base((uintptr_t)ws) {}
-  template <class T> T* take(size_t count) {
-    T* p = (T*)(base + off);
-    off = (off + count * sizeof(T) + 255) & ~(size_t)255;
-    return p;
-  }
-};
+// Every stage's regions come from cloud_grid.h's Bump, started behind the header.
 
 struct U8ToU64 {
   __host__ __device__ uint64_t operator()(uint8_t v) const { return v; }
@@ -707,7 +699,7 @@ static void vcycle(const MeshHdr* hdr, const SolveWs& w, int l, int R, hipStream
 }
 
 static size_t stage_bytes(int stage, int R, int64_t n, int64_t m) {
-  Bump b(nullptr);
+  Bump b(nullptr, SLG_MESH_HDR_BYTES);
   switch (stage) {
     case SLG_MESH_WS_GRID: grid_ws(b, n); break;
     case SLG_MESH_WS_SPLAT: splat_ws(b, R, n); break;
@@ -754,7 +746,7 @@ extern "C" int32_t slg_mesh_grid(const double* xyz, int64_t n, int32_t depth, do
     return slg_internal_fail(SLG_ERR_INVALID, "slg_mesh_grid: n <= 0, a NULL buffer, depth outside 2..10 or scale not finite and >= 1");
   if (n > slgcloud::kMaxPoints) return slg_internal_fail(SLG_ERR_UNSUPPORTED, "slg_mesh_grid: more than 2^30 points");
   if (int rc = bind("slg_mesh_grid", ws, ws_bytes, stage_bytes(SLG_MESH_WS_GRID, 0, n, 0))) return rc;
-  Bump b(ws);
+  Bump b(ws, SLG_MESH_HDR_BYTES);
   const GridWs g = grid_ws(b, n);
   hipStream_t st = (hipStream_t)stream;
   slgcloud::Ws w{};
@@ -771,7 +763,7 @@ extern "C" int32_t slg_mesh_splat(const double* xyz, const double* normals, int6
     return slg_internal_fail(SLG_ERR_INVALID, "slg_mesh_splat: n <= 0, a NULL buffer (the splat needs normals) or R no power of two in 1..1024");
   if (n > slgcloud::kMaxPoints) return slg_internal_fail(SLG_ERR_UNSUPPORTED, "slg_mesh_splat: more than 2^30 points");
   if (int rc = bind("slg_mesh_splat", ws, ws_bytes, stage_bytes(SLG_MESH_WS_SPLAT, R, n, 0))) return rc;
-  Bump b(ws);
+  Bump b(ws, SLG_MESH_HDR_BYTES);
   const SplatWs w = splat_ws(b, R, n);
   MeshHdr* hdr = (MeshHdr*)ws;
   hipStream_t st = (hipStream_t)stream;
@@ -805,7 +797,7 @@ extern "C" int32_t slg_mesh_solve(const double* f, int32_t R, int32_t cycles, vo
   if (!f || !chi_out || f == chi_out || cycles < 0 || !pow2_in(R, 4, 1 << kMaxDepth))
     return slg_internal_fail(SLG_ERR_INVALID, "slg_mesh_solve: a NULL buffer, chi == f, cycles < 0 or R no power of two in 4..1024");
   if (int rc = bind("slg_mesh_solve", ws, ws_bytes, stage_bytes(SLG_MESH_WS_SOLVE, R, 0, 0))) return rc;
-  Bump b(ws);
+  Bump b(ws, SLG_MESH_HDR_BYTES);
   SolveWs w = solve_ws(b, R);
   w.lv[0].u = chi_out;
   w.lv[0].f = (double*)f;                   // read only
@@ -827,7 +819,7 @@ extern "C" int32_t slg_mesh_iso(const double* chi, const double* xyz, int64_t n,
   if (!chi || !xyz || n <= 0) return slg_internal_fail(SLG_ERR_INVALID, "slg_mesh_iso: n <= 0 or a NULL buffer");
   if (n > slgcloud::kMaxPoints) return slg_internal_fail(SLG_ERR_UNSUPPORTED, "slg_mesh_iso: more than 2^30 points");
   if (int rc = bind("slg_mesh_iso", ws, ws_bytes, stage_bytes(SLG_MESH_WS_ISO, 0, n, 0))) return rc;
-  Bump b(ws);
+  Bump b(ws, SLG_MESH_HDR_BYTES);
   const IsoWs w = iso_ws(b, n);
   MeshHdr* hdr = (MeshHdr*)ws;
   hipStream_t st = (hipStream_t)stream;
@@ -842,7 +834,7 @@ extern "C" int32_t slg_mesh_count(const double* chi, int32_t R, void* ws, int64_
   if (!chi || R < 1 || R > (1 << kMaxDepth))
     return slg_internal_fail(SLG_ERR_INVALID, "slg_mesh_count: a NULL buffer or R outside 1..1024");
   if (int rc = bind("slg_mesh_count", ws, ws_bytes, stage_bytes(SLG_MESH_WS_EXTRACT, R, 0, 0))) return rc;
-  Bump b(ws);
+  Bump b(ws, SLG_MESH_HDR_BYTES);
   const ExtractWs w = extract_ws(b, R);
   MeshHdr* hdr = (MeshHdr*)ws;
   hipStream_t st = (hipStream_t)stream;
@@ -862,7 +854,7 @@ extern "C" int32_t slg_mesh_emit(const double* chi, const double* W, int32_t R, 
     return slg_internal_fail(SLG_ERR_INVALID, "slg_mesh_emit: a NULL buffer, R outside 1..1024 or a negative count");
   if (n_vertices >= (1ll << 31)) return slg_internal_fail(SLG_ERR_UNSUPPORTED, "slg_mesh_emit: 2^31 vertices or more");
   if (int rc = bind("slg_mesh_emit", ws, ws_bytes, stage_bytes(SLG_MESH_WS_EXTRACT, R, 0, 0))) return rc;
-  Bump b(ws);
+  Bump b(ws, SLG_MESH_HDR_BYTES);
   const ExtractWs w = extract_ws(b, R);
   const MeshHdr* hdr = (const MeshHdr*)ws;
   hipStream_t st = (hipStream_t)stream;
@@ -877,7 +869,7 @@ extern "C" int32_t slg_mesh_quantile(const double* values, int64_t n, double q, 
   if (!values || n <= 0 || !(q >= 0.0 && q <= 1.0))
     return slg_internal_fail(SLG_ERR_INVALID, "slg_mesh_quantile: n <= 0, a NULL buffer or q outside [0, 1]");
   if (int rc = bind("slg_mesh_quantile", ws, ws_bytes, stage_bytes(SLG_MESH_WS_QUANTILE, 0, n, 0))) return rc;
-  Bump b(ws);
+  Bump b(ws, SLG_MESH_HDR_BYTES);
   const QuantileWs w = quantile_ws(b, n);
   hipStream_t st = (hipStream_t)stream;
   size_t tb = w.tb, need = 0;
@@ -900,7 +892,7 @@ extern "C" int32_t slg_mesh_remove(const double* vertices, const double* densiti
     return slg_internal_fail(SLG_ERR_INVALID, "slg_mesh_remove: no vertices, a negative count or a NULL buffer");
   if (n_vertices >= (1ll << 31)) return slg_internal_fail(SLG_ERR_UNSUPPORTED, "slg_mesh_remove: 2^31 vertices or more");
   if (int rc = bind("slg_mesh_remove", ws, ws_bytes, stage_bytes(SLG_MESH_WS_REMOVE, 0, n_vertices, n_triangles))) return rc;
-  Bump b(ws);
+  Bump b(ws, SLG_MESH_HDR_BYTES);
   const RemoveWs w = remove_ws(b, n_vertices, n_triangles);
   MeshHdr* hdr = (MeshHdr*)ws;
   hipStream_t st = (hipStream_t)stream;

@@ -266,8 +266,8 @@ void normals_kernel(Hdr* hdr, const double* __restrict__ xyz, const double* __re
 }
 
 // knn_far_kernel (cloud_filter.hip) with the (d2, index) order: the wave merges its 64 sorted
-// lists by taking the smallest (d2, index) head until kk are taken or none is left; every lane
-// adds the same moments.
+// lists (wave_merge: the smallest (d2, index) head until kk are taken or none is left); every
+// lane adds the same moments.
 __global__ __launch_bounds__(64)
 void normals_far_kernel(const Hdr* hdr, const double* __restrict__ xyz, const double* __restrict__ sxyz,
                         const uint32_t* __restrict__ sidx, int64_t n, int k, double r2, double* __restrict__ normals,
@@ -283,25 +283,12 @@ void normals_far_kernel(const Hdr* hdr, const double* __restrict__ xyz, const do
     TopKI tk{lds + lane, (uint32_t*)(lds + (size_t)kk * 64) + lane, kk, 0, 0, -1.0, 0u};
     scan_range<true>(tk, sxyz, sidx, lane, (uint32_t)n, 64, p, r2);
     tk.sort();
-    int head = 0, m = 0;
     Moments M;
     M.clear();
-    for (int r = 0; r < kk; ++r) {
-      const bool have = head < tk.cnt;
-      const double v = have ? tk.lst[head * 64] : kInf;
-      const uint32_t vi = have ? tk.idx[head * 64] : kNone;
-      const double best = wave_min(v);
-      if (best == kInf) break;               // every list is used up (uniform over the wave)
-      uint32_t bi = v == best ? vi : kNone;
-      for (int s = 32; s > 0; s >>= 1) {
-        const uint32_t other = (uint32_t)__shfl_xor((int)bi, s, 64);
-        bi = other < bi ? other : bi;
-      }
-      if (have && v == best && vi == bi) ++head;
+    const int m = wave_merge<true>(tk, kk, [&](int, double, uint32_t bi) {
       const size_t o = 3 * (size_t)bi;
       M.add(xyz[o], xyz[o + 1], xyz[o + 2]);
-      ++m;
-    }
+    });
     if (lane == 0) normals_write(M, m, sidx[q], normals, cov_out, m_out);
   }
 }

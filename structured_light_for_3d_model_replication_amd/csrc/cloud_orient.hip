@@ -68,29 +68,24 @@ struct OrientWs {
   unsigned long long *best_w, *best_e, *emst_e, *tree_e;
 };
 
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-size_t orient_layout(void* base, size_t grid_bytes, int64_t n, int kk, OrientWs* w) {
-  size_t o = up256(grid_bytes);
-  auto take = [&](size_t bytes) { void* p = (void*)((uintptr_t)base + o); o = up256(o + bytes); return p; };
+void orient_layout(Bump& b, int64_t n, int kk, OrientWs* w) {
   const size_t N = (size_t)n, entries = (size_t)grid_of(n, 64) * kk * 64;
-  w->oh = (OHdr*)take(1024);
-  w->lst_d = (double*)take(entries * 8);
-  w->lst_i = (uint32_t*)take(entries * 4);
-  w->far_d = (double*)take((size_t)kFarBlocks * kk * 64 * 8);
-  w->far_i = (uint32_t*)take((size_t)kFarBlocks * kk * 64 * 4);
-  w->link = (uint32_t*)take(N * 4);
-  w->hook = (uint32_t*)take(N * 4);
-  w->scomp = (uint32_t*)take(N * 4);
-  w->cur = (uint32_t*)take(N * 4);
-  w->cand_j = (uint32_t*)take(N * 4);
-  w->sizes = (int32_t*)take(N * 4);
-  w->cand_d = (double*)take(N * 8);
-  w->best_w = (unsigned long long*)take(N * 8);
-  w->best_e = (unsigned long long*)take(N * 8);
-  w->emst_e = (unsigned long long*)take(N * 8);
-  w->tree_e = (unsigned long long*)take(N * 8);
-  return o;
+  w->oh = (OHdr*)b.take<uint8_t>(1024);
+  w->lst_d = b.take<double>(entries);
+  w->lst_i = b.take<uint32_t>(entries);
+  w->far_d = b.take<double>((size_t)kFarBlocks * kk * 64);
+  w->far_i = b.take<uint32_t>((size_t)kFarBlocks * kk * 64);
+  w->link = b.take<uint32_t>(N);
+  w->hook = b.take<uint32_t>(N);
+  w->scomp = b.take<uint32_t>(N);
+  w->cur = b.take<uint32_t>(N);
+  w->cand_j = b.take<uint32_t>(N);
+  w->sizes = b.take<int32_t>(N);
+  w->cand_d = b.take<double>(N);
+  w->best_w = b.take<unsigned long long>(N);
+  w->best_e = b.take<unsigned long long>(N);
+  w->emst_e = b.take<unsigned long long>(N);
+  w->tree_e = b.take<unsigned long long>(N);
 }
 
 // ---------------------------------------------------------------- the rules (one place each)
@@ -122,57 +117,20 @@ __device__ inline uint32_t edge_parity_rule(const double* __restrict__ nrm, uint
 __device__ inline unsigned long long load_u64(const unsigned long long* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
 
 // ---------------------------------------------------------------- lists
+// Plain kNN lists: cloud_grid.h's list kernels without the radius and without a count (kk <= n:
+// every list is full).
 __global__ __launch_bounds__(64)
 void orient_lists_kernel(Hdr* hdr, const double* __restrict__ sxyz, const uint32_t* __restrict__ sidx,
                          const uint64_t* __restrict__ ukeys, const uint32_t* __restrict__ ustart, int64_t n, int kk,
                          double* lst_d, uint32_t* lst_i, uint32_t* __restrict__ far) {
-  if (hdr->status) return;
-  const int64_t q = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  if (q >= n) return;
-  const size_t base = (size_t)blockIdx.x * kk * 64 + threadIdx.x;
-  TopKI tk{lst_d + base, lst_i + base, kk, 0, 0, -1.0, 0u};
-  if (!ring_walk<false>(hdr, sxyz, sidx, ukeys, ustart, q, 0.0, tk)) {
-    far[atomicAdd(&hdr->n_far, 1)] = (uint32_t)q;      // at most one entry per point: n entries
-    return;
-  }
-  tk.sort();
+  lists_body<false>(hdr, sxyz, sidx, ukeys, ustart, n, kk, 0.0, lst_d, lst_i, nullptr, far);
 }
 
-// fpfh_far_kernel's merge without the radius: each lane keeps the best kk of its stride of the
-// whole cloud, the wave takes the smallest (d2, index) head kk times (kk <= n: never used up).
 __global__ __launch_bounds__(64)
 void orient_lists_far_kernel(const Hdr* hdr, const double* __restrict__ sxyz, const uint32_t* __restrict__ sidx,
                              int64_t n, int kk, double* far_d, uint32_t* far_i, double* lst_d, uint32_t* lst_i,
                              const uint32_t* __restrict__ far) {
-  if (hdr->status) return;
-  const int lane = threadIdx.x;
-  const int nf = hdr->n_far;
-  const size_t scratch = (size_t)blockIdx.x * kk * 64 + lane;
-  for (int f = blockIdx.x; f < nf; f += gridDim.x) {
-    const int64_t q = far[f];
-    const double p[3] = {sxyz[3 * q], sxyz[3 * q + 1], sxyz[3 * q + 2]};
-    TopKI tk{far_d + scratch, far_i + scratch, kk, 0, 0, -1.0, 0u};
-    scan_range<false>(tk, sxyz, sidx, lane, (uint32_t)n, 64, p, 0.0);
-    tk.sort();
-    const size_t slot = (size_t)(q / 64) * kk * 64 + (size_t)(q % 64);
-    int head = 0;
-    for (int r = 0; r < kk; ++r) {
-      const bool have = head < tk.cnt;
-      const double v = have ? tk.lst[head * 64] : kInf;
-      const uint32_t vi = have ? tk.idx[head * 64] : kNone;
-      const double best = wave_min(v);
-      uint32_t bi = v == best ? vi : kNone;
-      for (int s = 32; s > 0; s >>= 1) {
-        const uint32_t other = (uint32_t)__shfl_xor((int)bi, s, 64);
-        bi = other < bi ? other : bi;
-      }
-      if (have && v == best && vi == bi) ++head;
-      if (lane == 0) {
-        lst_d[slot + (size_t)r * 64] = best;
-        lst_i[slot + (size_t)r * 64] = bi;
-      }
-    }
-  }
+  lists_far_body<false>(hdr, sxyz, sidx, n, kk, 0.0, far_d, far_i, lst_d, lst_i, nullptr, far);
 }
 
 // The lists by input index, row-major [n][kk].
@@ -619,15 +577,8 @@ int refuse(const char* who, const double* xyz, int64_t n, int32_t k) {
 }
 
 int orient_bind(const char* who, int64_t n, int kk, void* ws, int64_t ws_bytes, OrientWs* w) {
-  const int64_t grid_bytes = slg_filter_ws_bytes(n, 0);
-  if (grid_bytes < 0) return (int32_t)-grid_bytes;
-  int rc = begin_call(who, n, ws, -1, &w->grid);
-  if (rc) return rc;
-  const size_t total = orient_layout(ws, (size_t)grid_bytes, n, kk, w);
-  if (ws_bytes < 0 || (size_t)ws_bytes < total)
-    return slg_internal_fail(SLG_ERR_INVALID, "%s: workspace of %lld bytes, slg_orient_ws_bytes gives %lld", who,
-                             (long long)ws_bytes, (long long)total);
-  return SLG_OK;
+  return begin_ext_call(who, "slg_orient_ws_bytes", n, 0, ws, ws_bytes, &w->grid,
+                        [&](Bump& b) { orient_layout(b, n, kk, w); });
 }
 
 // Stage 1: the grid and the sorted lists.
@@ -704,10 +655,8 @@ extern "C" int64_t slg_orient_ws_bytes(int64_t n, int32_t k) {
   if (n > kMaxPoints || k > kOrientMaxK)
     return -(int64_t)slg_internal_fail(SLG_ERR_UNSUPPORTED, "slg_orient_ws_bytes: more than 2^30 points or k > %d",
                                        kOrientMaxK);
-  const int64_t grid_bytes = slg_filter_ws_bytes(n, 0);
-  if (grid_bytes < 0) return grid_bytes;
   OrientWs w;
-  return (int64_t)orient_layout(nullptr, (size_t)grid_bytes, n, (int)(n < k ? n : k), &w);
+  return ext_ws_bytes(n, 0, [&](Bump& b) { orient_layout(b, n, (int)(n < k ? n : k), &w); });
 }
 
 extern "C" int32_t slg_knn_lists(const double* xyz, int64_t n, int32_t k, void* ws, int64_t ws_bytes, uint32_t* idx_out,

@@ -34,33 +34,17 @@ struct PlaneWs {
   double* err;          // [batch][chunks]
 };
 
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-size_t plane_layout(void* base, size_t grid_bytes, int64_t n, int32_t batch, PlaneWs* w) {
-  size_t o = up256(grid_bytes);
-  auto take = [&](size_t bytes) { void* p = (void*)((uintptr_t)base + o); o = up256(o + bytes); return p; };
+void plane_layout(Bump& b, int64_t n, int32_t batch, PlaneWs* w) {
   const size_t nb = (size_t)grid_of(n, kChunk);
-  w->planes = (double*)take((size_t)batch * 4 * 8);
-  w->valid = (uint32_t*)take((size_t)batch * 4);
-  w->cnt = (int32_t*)take(nb * (size_t)batch * 4);
-  w->err = (double*)take(nb * (size_t)batch * 8);
-  return o;
+  w->planes = b.take<double>((size_t)batch * 4);
+  w->valid = b.take<uint32_t>((size_t)batch);
+  w->cnt = b.take<int32_t>(nb * (size_t)batch);
+  w->err = b.take<double>(nb * (size_t)batch);
 }
 
 // ---------------------------------------------------------------- the rules (one place each)
-// The finaliser of SplitMix64, as in cloud_ransac.hip (§13's mix).
-__device__ inline uint64_t plane_mix64_rule(uint64_t z) {
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
-// Draw k of trial t: an index below n from the hash's upper 32 bits by a multiply-high.
-__device__ inline uint32_t plane_draw_rule(uint64_t seed, uint64_t t, uint32_t k, uint32_t n) {
-  const uint64_t h = plane_mix64_rule(plane_mix64_rule(seed + 0x9E3779B97F4A7C15ull) + (t * 8ull + k));
-  return (uint32_t)(((h >> 32) * (uint64_t)n) >> 32);
-}
-
+// (mix64_rule and draw_rule, which cloud_ransac.hip shares, are in cloud_grid.h; a trial here
+// reserves kMaxN draws: draw k of trial t hashes t * 8 + k.)
 // abc / norm and d from a point of the plane; false (the zero plane) when the norm is zero.
 __device__ inline bool plane_normalise_rule(double x, double y, double z, const double* at, double* pl) {
   const double norm = sqrt((x * x + y * y) + z * z);
@@ -114,7 +98,7 @@ void plane_trials_kernel(const double* __restrict__ xyz, int64_t n, int rn, uint
 #pragma unroll
   for (int k = 0; k < kMaxN; ++k) {
     const bool use = k < rn;
-    c[k] = use ? plane_draw_rule(seed, t, (uint32_t)k, (uint32_t)n) : 0u;
+    c[k] = use ? draw_rule<kMaxN>(seed, t, (uint32_t)k, (uint32_t)n) : 0u;
 #pragma unroll
     for (int a = 0; a < 3; ++a) p[k][a] = use ? xyz[3 * (size_t)c[k] + a] : 0.0;
 #pragma unroll
@@ -336,15 +320,8 @@ void plane_refit_final_kernel(const Hdr* hdr, const double* __restrict__ part, i
 }
 
 int plane_bind(const char* who, int64_t n, int32_t batch, void* ws, int64_t ws_bytes, PlaneWs* w) {
-  const int64_t grid_bytes = slg_filter_ws_bytes(n, 0);
-  if (grid_bytes < 0) return (int32_t)-grid_bytes;
-  int rc = begin_call(who, n, ws, -1, &w->grid);
-  if (rc) return rc;
-  const size_t total = plane_layout(ws, (size_t)grid_bytes, n, batch, w);
-  if (ws_bytes < 0 || (size_t)ws_bytes < total)
-    return slg_internal_fail(SLG_ERR_INVALID, "%s: workspace of %lld bytes, slg_plane_ws_bytes gives %lld", who,
-                             (long long)ws_bytes, (long long)total);
-  return SLG_OK;
+  return begin_ext_call(who, "slg_plane_ws_bytes", n, 0, ws, ws_bytes, &w->grid,
+                        [&](Bump& b) { plane_layout(b, n, batch, w); });
 }
 
 }  // namespace
@@ -357,10 +334,8 @@ extern "C" int64_t slg_plane_ws_bytes(int64_t n, int32_t batch) {
   if (n > kMaxPoints || batch > kMaxBatch)
     return -(int64_t)slg_internal_fail(SLG_ERR_UNSUPPORTED, "slg_plane_ws_bytes: more than 2^30 points or batch > %d",
                                        kMaxBatch);
-  const int64_t grid_bytes = slg_filter_ws_bytes(n, 0);
-  if (grid_bytes < 0) return grid_bytes;
   PlaneWs w;
-  return (int64_t)plane_layout(nullptr, (size_t)grid_bytes, n, batch, &w);
+  return ext_ws_bytes(n, 0, [&](Bump& b) { plane_layout(b, n, batch, &w); });
 }
 
 extern "C" int32_t slg_plane_batch(const double* xyz, int64_t n, double distance_threshold, int32_t ransac_n, int64_t seed,

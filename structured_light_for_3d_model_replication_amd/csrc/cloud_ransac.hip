@@ -23,10 +23,12 @@ constexpr int kRecordStride = 32;      // doubles per evaluation record (SLG_RAN
 constexpr int kEvalRows = 32;          // hypotheses evaluated side by side (grid.y); the rest by stride
 constexpr int kHornSweeps = 6;         // cyclic Jacobi sweeps on Horn's 4x4 (DESIGN.md §13 says why)
 constexpr int kFlagEdge = 1, kFlagDistance = 2;
+constexpr int kDrawStride = 4;         // draw k of trial t hashes t * 4 + k
 
 struct RansacState {    // 256 bytes behind the target grid's workspace
   int32_t n_pass;       // passing trials of the batch in flight
 };
+static_assert(sizeof(RansacState) <= 256, "state");
 
 struct RansacWs {
   Ws grid;              // the target's grid; its header carries the status word and far_count
@@ -38,34 +40,18 @@ struct RansacWs {
   double* part;         // [batch][blocks of kChunk source points][2] n_corr, err2
 };
 
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-size_t ransac_layout(void* base, size_t grid_bytes, int64_t ns, int32_t batch, RansacWs* w) {
-  size_t o = up256(grid_bytes);
-  auto take = [&](size_t bytes) { void* p = (void*)((uintptr_t)base + o); o = up256(o + bytes); return p; };
-  w->st = (RansacState*)take(256);
-  w->flags = (uint32_t*)take((size_t)batch * 4);
-  w->pass = (uint32_t*)take((size_t)batch * 4);
-  w->picks = (int32_t*)take((size_t)batch * 12);
-  w->T = (double*)take((size_t)batch * 12 * 8);
-  w->part = (double*)take((size_t)batch * grid_of(ns, kChunk) * 2 * 8);
-  return o;
+void ransac_layout(Bump& b, int64_t ns, int32_t batch, RansacWs* w) {
+  w->st = b.take<RansacState>(1);
+  w->flags = b.take<uint32_t>((size_t)batch);
+  w->pass = b.take<uint32_t>((size_t)batch);
+  w->picks = b.take<int32_t>((size_t)batch * 3);
+  w->T = b.take<double>((size_t)batch * 12);
+  w->part = b.take<double>((size_t)batch * grid_of(ns, kChunk) * 2);
 }
 
 // ---------------------------------------------------------------- the rules (one place each)
-// The finaliser of SplitMix64 (Steele, Lea, Flood 2014; Stafford's mix 13): integer operations only.
-__device__ inline uint64_t mix64_rule(uint64_t z) {
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
-// Draw k of trial t: an index below m from the hash's upper 32 bits by a multiply-high.
-__device__ inline uint32_t draw_rule(uint64_t seed, uint64_t t, uint32_t k, uint32_t m) {
-  const uint64_t h = mix64_rule(mix64_rule(seed + 0x9E3779B97F4A7C15ull) + (t * 4ull + k));
-  return (uint32_t)(((h >> 32) * (uint64_t)m) >> 32);
-}
-
+// (mix64_rule and draw_rule, which cloud_plane.hip shares, are in cloud_grid.h; a trial here
+// reserves kDrawStride draws.)
 // CorrespondenceCheckerBasedOnEdgeLength on squares (ours: Open3D compares the lengths).
 __device__ inline bool edge_rule(const double* sa, const double* sb, const double* ta, const double* tb, double e2) {
   const double ds2 = d2_rule(sa[0] - sb[0], sa[1] - sb[1], sa[2] - sb[2]);
@@ -193,7 +179,7 @@ void ransac_trials_kernel(Hdr* hdr, const double* __restrict__ src, int64_t ns, 
   bool ok = true;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    c[k] = draw_rule(seed, t, (uint32_t)k, (uint32_t)m);
+    c[k] = draw_rule<kDrawStride>(seed, t, (uint32_t)k, (uint32_t)m);
     const int64_t si = pairs[2 * (size_t)c[k]], ti = pairs[2 * (size_t)c[k] + 1];
     const bool in = si >= 0 && si < ns && ti >= 0 && ti < nt;
     if (!in) atomicOr(&hdr->status, SLG_FILTER_BAD_INDEX);
@@ -391,10 +377,8 @@ extern "C" int64_t slg_ransac_ws_bytes(int64_t n_source, int64_t n_target, int32
   if (n_source > kMaxPoints || n_target > kMaxPoints || batch > kMaxBatch)
     return -(int64_t)slg_internal_fail(SLG_ERR_UNSUPPORTED, "slg_ransac_ws_bytes: more than 2^30 points or batch > %d",
                                        kMaxBatch);
-  const int64_t grid_bytes = slg_filter_ws_bytes(n_target, kRansacGridK);
-  if (grid_bytes < 0) return grid_bytes;
   RansacWs w;
-  return (int64_t)ransac_layout(nullptr, (size_t)grid_bytes, n_source, batch, &w);
+  return ext_ws_bytes(n_target, kRansacGridK, [&](Bump& b) { ransac_layout(b, n_source, batch, &w); });
 }
 
 extern "C" int32_t slg_ransac_prepare(const double* tgt_xyz, int64_t n_target, void* ws, int64_t ws_bytes,
@@ -421,15 +405,10 @@ extern "C" int32_t slg_ransac_batch(const double* src_xyz, int64_t n_source, con
   if (n_source > kMaxPoints || n_pairs > kMaxPoints || batch > kMaxBatch)
     return slg_internal_fail(SLG_ERR_UNSUPPORTED, "slg_ransac_batch: more than 2^30 points or pairs, or batch > %d",
                              kMaxBatch);
-  const int64_t grid_bytes = slg_filter_ws_bytes(n_target, kRansacGridK);
-  if (grid_bytes < 0) return (int32_t)-grid_bytes;
   RansacWs w;
-  int rc = begin_call("slg_ransac_batch", n_target, ws, -1, &w.grid);
+  int rc = begin_ext_call("slg_ransac_batch", "slg_ransac_ws_bytes", n_target, kRansacGridK, ws, ws_bytes, &w.grid,
+                          [&](Bump& b) { ransac_layout(b, n_source, batch, &w); });
   if (rc) return rc;
-  const size_t total = ransac_layout(ws, (size_t)grid_bytes, n_source, batch, &w);
-  if (ws_bytes < 0 || (size_t)ws_bytes < total)
-    return slg_internal_fail(SLG_ERR_INVALID, "slg_ransac_batch: workspace of %lld bytes, slg_ransac_ws_bytes gives %lld",
-                             (long long)ws_bytes, (long long)total);
   hipStream_t st = (hipStream_t)stream;
   const Ws& g = w.grid;
   const double e2 = edge_length * edge_length, dist2 = max_dist * max_dist;

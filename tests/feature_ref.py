@@ -225,23 +225,39 @@ def mix64(z):
     return z ^ (z >> 31)
 
 
-def draw(seed, t, k, m):
-    """Draw ``k`` of trial ``t``: an index below ``m`` from the upper 32 bits by a multiply-high."""
-    h = mix64(mix64(seed + 0x9E3779B97F4A7C15) + (t * 4 + k))
+def draw_rule(seed, t, k, m, stride):
+    """Draw ``k`` of trial ``t``, with ``stride`` draws reserved per trial (``draw_rule<kStride>`` of
+    ``csrc/cloud_grid.h``): an index below ``m`` from the upper 32 bits by a multiply-high."""
+    h = mix64(mix64(seed + 0x9E3779B97F4A7C15) + (t * stride + k))
     return ((h >> 32) * m) >> 32
 
 
-def draws(seed, t0, count, m):
-    """int64 [count, 3]: :func:`draw` for the trials ``t0 .. t0 + count - 1``, on uint64 arrays."""
+def draw_table(seed, t0, count, width, m, stride):
+    """int64 [count, width]: :func:`draw_rule` for the draws ``0 .. width - 1`` of the trials
+    ``t0 .. t0 + count - 1``, on uint64 arrays."""
     def mix(z):
         z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
         z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
         return z ^ (z >> np.uint64(31))
     with np.errstate(over="ignore"):
         base = np.uint64(mix64(seed + 0x9E3779B97F4A7C15))
-        tk = (np.arange(t0, t0 + count, dtype=np.uint64)[:, None] * np.uint64(4) + np.arange(3, dtype=np.uint64)[None, :])
+        tk = (np.arange(t0, t0 + count, dtype=np.uint64)[:, None] * np.uint64(stride)
+              + np.arange(width, dtype=np.uint64)[None, :])
         h = mix(base + tk)
         return (((h >> np.uint64(32)) * np.uint64(m)) >> np.uint64(32)).astype(np.int64)
+
+
+DRAW_STRIDE = 4                     # kDrawStride of csrc/cloud_ransac.hip
+
+
+def draw(seed, t, k, m):
+    """The registration RANSAC's draw ``k`` of trial ``t``."""
+    return draw_rule(seed, t, k, m, DRAW_STRIDE)
+
+
+def draws(seed, t0, count, m):
+    """int64 [count, 3]: :func:`draw` for the trials ``t0 .. t0 + count - 1``."""
+    return draw_table(seed, t0, count, 3, m, DRAW_STRIDE)
 
 
 def edge_ok(S, D, e):

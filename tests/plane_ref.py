@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from feature_ref import MASK, mix64
+from feature_ref import MASK, draw_rule, draw_table  # noqa: F401  (MASK: the tests' 64-bit seeds)
 
 CHUNK = 2048                        # kChunk of csrc/cloud_grid.h: the order of err
 BATCH = 256                         # cloud.PLANE_BATCH
@@ -24,24 +24,14 @@ PROBABILITY = 0.99999999
 
 # ------------------------------------------------------------------ draws
 def plane_draw_rule(seed, t, k, n):
-    """Draw ``k`` of trial ``t`` on Python integers: an index below ``n``."""
-    h = mix64(mix64(seed + 0x9E3779B97F4A7C15) + ((t * 8 + k) & MASK))
-    return ((h >> 32) * n) >> 32
+    """Draw ``k`` of trial ``t`` on Python integers: an index below ``n`` (a trial reserves
+    ``MAX_N`` draws)."""
+    return draw_rule(seed, t, k, n, MAX_N)
 
 
 def draws(seed, t0, count, ransac_n, n):
-    """int64 [count, ransac_n]: :func:`plane_draw_rule` for the trials ``t0 .. t0 + count - 1``, on
-    uint64 arrays."""
-    def mix(z):
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        return z ^ (z >> np.uint64(31))
-    with np.errstate(over="ignore"):
-        base = np.uint64(mix64(seed + 0x9E3779B97F4A7C15))
-        tk = (np.arange(t0, t0 + count, dtype=np.uint64)[:, None] * np.uint64(8)
-              + np.arange(ransac_n, dtype=np.uint64)[None, :])
-        h = mix(base + tk)
-        return (((h >> np.uint64(32)) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
+    """int64 [count, ransac_n]: :func:`plane_draw_rule` for the trials ``t0 .. t0 + count - 1``."""
+    return draw_table(seed, t0, count, ransac_n, n, MAX_N)
 
 
 def distinct(c):

@@ -261,7 +261,7 @@ def main():
         wpc = CL.PointCloud(P, np.concatenate([C0, np.full((int(wall.sum()), 3), 200, np.uint8)]))
         nw, dev = len(wpc), wpc.xyz.device
         L, B = CL.N.lib(), CL.PLANE_BATCH
-        ws = CL._workspace(0, 0, dev, need=L.slg_plane_ws_bytes(nw, B))
+        ws = CL._workspace(dev, L.slg_plane_ws_bytes(nw, B))
         recs = torch.empty((B, CL.N.PLANE_RECORD_STRIDE), dtype=torch.float64, device=dev)
 
         def launch():                                        # the batch's three kernels, no read-back
