@@ -26,9 +26,9 @@ import sys
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
-# the compiled files; the headers beside them (internal.h, workspace.h, otsu.h, code_object.h,
-# cloud_grid.h) enter the digest through their directory
-SRCS = [os.path.join(CSRC, n) for n in ("slgpu.hip", "ply.hip", "color_gray.hip", "png_device.hip",
+# the compiled files; the headers beside them (DESIGN.md §11 lists them) enter the digest
+# through their directory
+SRCS = [os.path.join(CSRC, n) for n in ("slgpu.hip", "stats.hip", "ply.hip", "color_gray.hip", "png_device.hip",
                                         "cloud_grid.hip", "cloud_filter.hip", "cloud_cluster.hip",
                                         "cloud_normals.hip", "cloud_icp.hip", "cloud_feature.hip",
                                         "cloud_ransac.hip", "cloud_plane.hip", "cloud_orient.hip", "cloud_mesh.hip", "code_object.cpp",

@@ -1,7 +1,7 @@
 // otsu.h -- device code of the mask thresholds: wave helpers, the one-wave Otsu (OpenCV's
 // operation order), the NumPy percentile, the matrix-core histograms, and the "thresholds from
 // summed histograms / from per-tile partials" tails shared by stats_kernel, parts_kernel,
-// hist_thresholds_kernel and main3's finishing workgroups (slgpu.hip).  Device only; every name
+// hist_thresholds_kernel (stats.hip) and main3's finishing workgroups (slgpu.hip).  Device only; every name
 // is TU-local.  SLG_OTSU_MARK(k): a hook per part of otsu_wave (tools/otsu_probe.hip).
 #pragma once
 #include <hip/hip_runtime.h>

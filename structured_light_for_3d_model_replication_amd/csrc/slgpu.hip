@@ -1,31 +1,18 @@
-// slgpu.hip -- the structured-light hot path on MI355X (gfx950, CDNA4): mask thresholds, the
-// fused decode + triangulate kernel, their launch code and the C ABI entries that run them.
+// slgpu.hip -- the structured-light hot path on MI355X (gfx950, CDNA4): the fused decode +
+// triangulate kernel, its launch code and the C ABI entries that run it.
 //
 // Path (reference): Gray-code decode  server/processing.py:28-124, server/sl_system.py:516-588
 //                   ray-plane triangulation  server/processing.py:127-234, sl_system.py:592-661
-// C ABI: include/slgpu.h.  Design and rooflines: DESIGN.md.
-//
-// Beside this file: workspace.h (the per-view workspace layout), otsu.h (histogram / Otsu /
-// percentile device code the kernels below share), internal.h (last-error entry, launch check),
-// code_object.cpp (which kernels the built library carries), ply.hip (PLY text), color_gray.hip
-// (colour ingest), png_device.hip, png_gray.cpp, the device cloud steps (cloud_grid.h,
-// cloud_grid.hip, cloud_filter.hip, cloud_cluster.hip, cloud_normals.hip), gather.cpp.
+// C ABI: include/slgpu.h.  Design and rooflines: DESIGN.md; the files of csrc/: DESIGN.md §11.
+// main3_kernel and everything it inlines (fused_params.h, decode.h, triangulate.h, lookback.h,
+// carried_hist.h, otsu.h) stay in this one translation unit and in the anonymous namespace:
+// main3_symbol() spells the mangled name.
 //
 // Kernels here
-//   stats_kernel      white/black histograms (+ max contrast) -> last-arriving workgroup turns
-//                     them into integer mask thresholds (Otsu as OpenCV, or NumPy percentile);
-//                     also zeroes the compaction state of the next main launch.
-//   parts_kernel, hist_thresholds_kernel  the same thresholds from per-tile partial histograms a
-//                     fused launch carried, or from histograms summed over the ranks' bands.
 //   main3_kernel<...> fused decode + triangulate + ordered compaction, one 4096-pixel tile per
-//                     workgroup (512 lanes x 8 pixels), up to 16 views per launch: the mask
-//                     first (white/black), then the used pattern frames only in lanes holding a
-//                     valid pixel, with 8-byte-per-lane coalesced loads (instances specialised on
-//                     the common decode plans issue them all unconditionally), SWAR byte compares,
-//                     packed 16-bit Gray->binary, wave-private LDS compaction of valid pixels,
-//                     fp64 ray-plane intersection, decoupled look-back over static tile ids,
-//                     compacted stores straight from registers; the grid's first workgroups
-//                     can turn a carried batch's Otsu partials into thresholds.
+//                     workgroup, up to 16 views per launch (phases A to D: the comment at the
+//                     kernel); the grid's first workgroups can turn a carried batch's Otsu
+//                     partials into thresholds.
 //   decode_maps_kernel  the decode alone, to correspondence maps (slg_decode).
 //   row_tail_kernel   row_mode 2: moves the row cloud behind the column cloud.
 //   set_arena_kernel  the resident-job arena words of the workspace headers.
@@ -37,14 +24,11 @@
 // -ffp-contract=off (no FMA contraction), IEEE-correct f64 division and sqrt, so the fp64
 // results equal the reference bit for bit; integer/byte work is exact by construction.
 #include <hip/hip_runtime.h>
-#include <stddef.h>
-#include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
 #include <string.h>
 #include <limits.h>
 #include <type_traits>
-#include <utility>
 #include <stdlib.h>
 #include <math.h>
 #include <string>
@@ -53,947 +37,19 @@
 #include <mutex>
 #include <dlfcn.h>
 
+#include "capture_checks.h"
 #include "code_object.h"
-#include "internal.h"
-#include "otsu.h"
-#include "workspace.h"
+#include "fused_params.h"
+#include "decode.h"
+#include "triangulate.h"
+#include "lookback.h"
+#include "carried_hist.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int kMapsPx = kBlock * kPx;       // 2048 pixels per decode_maps workgroup
-constexpr int kMaxBits = 15;                // packed 16-bit code lanes
-constexpr uint64_t kFlagAgg = 1ull << 62;
-constexpr uint64_t kFlagInc = 2ull << 62;
-constexpr uint64_t kValMask = (1ull << 62) - 1;
-
-// ------------------------------------------------------------------ small helpers
-__device__ inline uint64_t ld_state(const uint64_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ inline void st_state(uint64_t* p, uint64_t v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-#ifndef SLG_FRAME_BUFFER_LOADS
-#define SLG_FRAME_BUFFER_LOADS 1           // frame loads as buffer loads (scalar base, 32-bit lane offset)
-#endif
-// Per-byte unsigned p > i on 4 packed bytes: 0x80 in every byte lane where p > i.
-__device__ inline uint32_t gt_u8x4(uint32_t p, uint32_t i) {
-  // per byte p > i in bit 7 (other bits garbage: callers mask with 0x80808080):
-  // f(p, i, d) = (p & ~i) | (~(p ^ i) & ~d), d = (i | 0x80) - (p & 0x7f) per byte, one v_bitop3
-  const uint32_t d = (i | 0x80808080u) - (p & 0x7f7f7f7fu);
-  uint32_t r;
-  asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x71" : "=v"(r) : "v"(p), "v"(i), "v"(d));
-  return r;
-}
-
-// Gray -> binary on two packed 16-bit lanes (values < 2^15): prefix XOR from the top.
-__device__ inline uint32_t gray2bin_x2(uint32_t x) {
-  x ^= (x >> 1) & 0x7fff7fffu;
-  x ^= (x >> 2) & 0x3fff3fffu;
-  x ^= (x >> 4) & 0x0fff0fffu;
-  x ^= (x >> 8) & 0x00ff00ffu;
-  return x;
-}
-
-// ------------------------------------------------------------------ stats kernel
-constexpr int kMaxBatch = 16;               // views per batched stats launch (blockIdx.y)
-constexpr int kStatsPx = 32;                // pixels per lane per stats iteration
-constexpr int kStatsBlocks = 64;            // stats workgroups per view (at most), percentile path
-#ifndef SLG_STATS_OTSU_BLOCKS
-#define SLG_STATS_OTSU_BLOCKS 64                 // 128: 2.6% and 256: 10% slower bench (slot contention)
-#endif
-constexpr int kStatsBlocksOtsu = SLG_STATS_OTSU_BLOCKS;   // matrix-core Otsu path
-#ifndef SLG_STATS_BLOCKS_ONE
-#define SLG_STATS_BLOCKS_ONE 256   // r3ao: 64 -> 51.7, 128 -> 42.2, 256 -> 40.0, 512 -> 39.9 us (1080p, Otsu)
-#endif
-constexpr int kStatsBlocksOne = SLG_STATS_BLOCKS_ONE;   // one-view launches (nothing runs beside them)
-#ifndef SLG_OTSU_ONE_CHUNKS
-#define SLG_OTSU_ONE_CHUNKS 2
-#endif
-constexpr int kOtsuOneChunks = SLG_OTSU_ONE_CHUNKS;
-
-struct StatsParams {
-  const uint8_t* white[kMaxBatch];
-  const uint8_t* black[kMaxBatch];
-  WsHeader* wsv[kMaxBatch];
-  int64_t n_px;
-  int64_t n_state_words;   // look-back words zeroed here for the next main launch
-  int32_t thresh_mode;
-  int32_t pad;
-  double shadow_val;
-  double contrast_val;
-  int32_t pad2[2];
-  const uint32_t* parts[kMaxBatch];   // parts_kernel: per-tile partial histograms of each view
-  int64_t n_parts;                    // tiles per view
-  int64_t pad_zero;                   // zero pixels counted past n_px (removed from bin 0)
-  uint32_t* hist_out;                 // one view, histograms only (slg_decode_histograms): no thresholds
-};
-
-#ifndef SLG_STATS_MINB
-#define SLG_STATS_MINB 1     // stats_kernel workgroups per CU its registers are budgeted for
-#endif
-
-__global__ __launch_bounds__(kBlock, SLG_STATS_MINB) void stats_kernel(StatsParams p) {
-  // 16 sub-histograms per kind (wave x lane&3), rows padded to 257 words so the copies of one
-  // bin sit in different banks: a flat background costs at most 16-way same-address adds.
-  constexpr int kRow = 257;
-  __shared__ __attribute__((aligned(16))) uint32_t sh[16 * 2 * kRow];
-  static_assert(512 * 4 + 2 * kOtsuLds * 8 <= 16 * 2 * kRow * 4, "Otsu tail: histograms + two waves' LDS");
-  __shared__ uint32_t s_maxd;
-  __shared__ uint32_t s_last;
-  __shared__ int64_t s_above[2];
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6;
-  const int view = blockIdx.y;               // batched launches: one grid row per view
-  WsHeader* ws = p.wsv[view];
-  const uint8_t* white = p.white[view];
-  const uint8_t* black = p.black[view];
-  uint32_t* hist_part = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ws) + kHistPartOff);
-  uint64_t* states = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(ws) + states_off(p.n_px));
-
-  // Arm the compaction state of the following main launch (ordered by the kernel boundary).
-  for (int64_t i = int64_t(blockIdx.x) * kBlock + tid; i < p.n_state_words; i += int64_t(gridDim.x) * kBlock)
-    states[i] = 0;
-  if (blockIdx.x == 0 && tid == 0) ws->lb_ticket = ws->lb_ticket_row = 0;
-
-  if (p.thresh_mode == SLG_THRESH_MANUAL) {
-    if (blockIdx.x == 0 && tid < 2) {
-      const double thr = tid == 0 ? p.shadow_val : p.contrast_val;
-      const int m = int_threshold(thr, tid == 0 ? 0 : -255);
-      if (tid == 0) { ws->smin = m; ws->thr_s = thr; } else { ws->cmin = m; ws->thr_c = thr; }
-      ws->above[tid] = p.n_px;                 // manual thresholds: no histogram, no bound
-    }
-    if (blockIdx.x == 0 && tid == 0) arena_reserve(ws, p.n_px, p.n_px);
-    return;
-  }
-
-  for (int i = tid; i < 16 * 2 * kRow; i += kBlock) sh[i] = 0;
-  if (tid == 0) s_maxd = 0;
-  __syncthreads();
-
-  // hist kinds: otsu -> [0] white, [1] clip(white-black); percentile -> [0] black.
-  const bool otsu = p.thresh_mode == SLG_THRESH_OTSU;
-  if (otsu) {                                  // matrix-core histograms (hist_chunk_dpp)
-    v4i32 acc_w = {0, 0, 0, 0}, acc_d = {0, 0, 0, 0};
-    const int lane = tid & 63;
-    const int64_t step = int64_t(gridDim.x) * (kBlock / 64) * kHistChunk;
-    int64_t c = (int64_t(blockIdx.x) * (kBlock / 64) + wave) * kHistChunk;
-    uint32_t w[4], d[4];
-    if (c < p.n_px) hist_load(white, black, c, p.n_px, w, d);
-    for (; c < p.n_px; c += step) {            // next chunk's loads in flight during the MFMAs
-      uint32_t wn[4], dn[4];
-      const bool more = c + step < p.n_px;
-      if (more) hist_load(white, black, c + step, p.n_px, wn, dn);
-      hist_chunk_dpp(w, d, acc_w, acc_d);
-      if (more) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { w[q] = wn[q]; d[q] = dn[q]; }
-      }
-    }
-    acc_w = hist_from_cumulative(acc_w);
-    acc_d = hist_from_cumulative(acc_d);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {              // wave sub-histograms: row-major bins 16*row + col
-      const int bin = 16 * (4 * (lane >> 4) + r) + (lane & 15);
-      if (acc_w[r]) atomicAdd(&sh[(2 * wave) * kRow + bin], uint32_t(acc_w[r]) >> 8);
-      if (acc_d[r]) atomicAdd(&sh[(2 * wave + 1) * kRow + bin], uint32_t(acc_d[r]) >> 8);
-    }
-  }
-  // percentile: LDS adds into 16 sub-histograms, kStatsPx consecutive pixels per lane and step
-  uint32_t local_max = 0;
-  if (!otsu) {
-    uint32_t* h0 = sh + (4 * wave + (tid & 3)) * 2 * kRow;
-    const int64_t per_block = int64_t(kBlock) * kStatsPx;
-    for (int64_t b0 = int64_t(blockIdx.x) * per_block; b0 < p.n_px; b0 += int64_t(gridDim.x) * per_block) {
-      const int64_t px0 = b0 + int64_t(tid) * kStatsPx;
-      uint2 w[kStatsPx / 8], b[kStatsPx / 8];
-#pragma unroll
-      for (int q = 0; q < kStatsPx / 8; ++q) {
-        const int64_t o = px0 + 8 * q < p.n_px ? px0 + 8 * q : 0;   // frames readable to round_up(n, 8)
-        w[q] = *reinterpret_cast<const uint2*>(white + o);
-        b[q] = *reinterpret_cast<const uint2*>(black + o);
-      }
-      // (a guard, not a break: with the break the loop stayed rolled and w[] / b[] went to
-      // scratch, indexed at run time)
-#pragma unroll
-      for (int k = 0; k < kStatsPx; ++k) {
-        if (px0 + k < p.n_px) {
-          const uint2 wq = w[k >> 3], bq = b[k >> 3];
-          const int wv = (((k & 7) < 4 ? wq.x : wq.y) >> (8 * (k & 3))) & 0xff;
-          const int bv = (((k & 7) < 4 ? bq.x : bq.y) >> (8 * (k & 3))) & 0xff;
-          atomicAdd(&h0[bv], 1u);
-          local_max = max(local_max, uint32_t(wv - bv + 256));
-        }
-      }
-    }
-  }
-  if (!otsu) atomicMax(&s_maxd, local_max);
-  __syncthreads();
-  for (int i = tid; i < 2 * 256; i += kBlock) {
-    const int kind = i >> 8, bin = i & 255;
-    uint32_t v = 0;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) v += sh[(2 * c + kind) * kRow + bin];
-    if (v) atomicAdd(hist_part + (blockIdx.x % kHistCopies) * 512 + i, v);
-  }
-  if (!otsu && tid == 0 && s_maxd) atomicMax(&ws->max_diff_enc, s_maxd);
-
-  // Publish (every wave drains its atomics, barrier) then take a ticket.  Hardware assumption
-  // (no release / acquire fences): what the last arriver reads -- the histogram copies,
-  // max_diff_enc -- is written and read by agent-scope atomics only, which gfx950 performs at
-  // the L2 that owns the address (the device's point of coherence for agent scope, whichever
-  // XCD issues them); a returned vmcnt means the add has been performed there, so a ticket
-  // taken after vmcnt(0) orders every earlier add before the last arriver's atomic loads.  No
-  // L2 write-back or invalidate is needed (an agent-scope fence is one of each, per workgroup).
-  // tests/test_gpu_configs.py::test_concurrent_stats_thresholds checks the thresholds of many
-  // concurrent multi-view launches against the oracle.
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    const uint32_t t = __hip_atomic_fetch_add(&ws->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = (t == gridDim.x - 1) ? 1u : 0u;
-  }
-  __syncthreads();
-  if (!s_last) return;
-
-  // Last arriver: read the global histograms, compute thresholds, reset for reuse.
-  uint32_t* hg = sh;                           // reuse the sub-histograms for the global ones
-  sum_hist_copies(hist_part, tid, otsu ? uint32_t(p.pad_zero) : 0u, hg);
-  if (tid == 0) s_maxd = __hip_atomic_load(&ws->max_diff_enc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();
-  if (p.hist_out) {                            // histograms only: a band of a view split over ranks
-    for (int i = tid; i < 512; i += kBlock) p.hist_out[i] = hg[i];
-    if (tid == 0) p.hist_out[512] = s_maxd;
-  } else {
-    set_thresholds(hg, s_maxd, p.n_px, otsu, ws, reinterpret_cast<double*>(sh + 512), s_above);
-  }
-  for (int i = tid; i < kHistCopies * 512; i += kBlock) hist_part[i] = 0;
-  if (tid == 0) { ws->max_diff_enc = 0; ws->ticket = 0; }
-}
-
-// Thresholds of a view whose histograms were summed over the bands of rows the ranks hold
-// (slg_thresholds_from_histograms; SURVEY 8(e), the one exchange step of a single-view split):
-// block 0 runs set_thresholds on hist[513] (as slg_decode_histograms wrote it, summed), every
-// block zeroes this band's look-back words for the following fused launch (kernel boundary).
-__global__ __launch_bounds__(kBlock) void hist_thresholds_kernel(const uint32_t* hist, WsHeader* ws, int64_t n_px,
-                                                                 int32_t thresh_mode, int64_t n_state_words) {
-  __shared__ __attribute__((aligned(16))) uint32_t hg[512 + 4 * kOtsuLds];
-  __shared__ int64_t s_above[2];
-  const int tid = threadIdx.x;
-  uint64_t* states = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(ws) + states_off(0));
-  for (int64_t i = int64_t(blockIdx.x) * kBlock + tid; i < n_state_words; i += int64_t(gridDim.x) * kBlock)
-    states[i] = 0;
-  if (blockIdx.x != 0) return;
-  if (tid == 0) ws->lb_ticket = ws->lb_ticket_row = 0;
-  for (int i = tid; i < 512; i += kBlock) hg[i] = hist[i];
-  __syncthreads();
-  set_thresholds(hg, hist[512], n_px, thresh_mode == SLG_THRESH_OTSU, ws, reinterpret_cast<double*>(hg + 512), s_above);
-}
-
-__global__ __launch_bounds__(kBlock) void parts_kernel(StatsParams p) {
-  __shared__ __attribute__((aligned(16))) uint32_t hg[kPartsLdsWords];   // + the Otsu tail's LDS
-  __shared__ uint32_t s_last;
-  otsu_from_parts(p.parts[blockIdx.y], p.wsv[blockIdx.y], p.n_parts, p.n_px, p.n_state_words, p.pad_zero,
-                  int(blockIdx.x), int(gridDim.x), hg, &s_last);
-}
-
-// ------------------------------------------------------------------ main kernel
-// Decode plan of one view: per axis, the frame index of the first pattern, the pairs to read,
-// the pre-shift and the post-shift (make_plan).
-struct Plan {
-  int32_t col_first, col_pairs, col_pre, col_post;
-  int32_t row_first, row_pairs, row_pre, row_post;
-};
-
-struct MainParams {
-  // frames source
-  const uint8_t* frames;
-  int64_t stride;
-  // maps source
-  const int32_t* in_col;
-  const int32_t* in_row;
-  const uint8_t* in_mask;
-  // common
-  const uint8_t* texture;
-  int64_t n_px;
-  int32_t width;
-  Plan plan;
-  // maps output
-  int32_t* out_col;
-  int32_t* out_row;
-  uint8_t* out_mask;
-  // calibration
-  const double* rays;
-  double fx, fy, cx, cy;
-  double rfx, rfy;            // RN(1/fx), RN(1/fy) when div_fast (Markstein divisions)
-  int32_t div_fast;
-  int32_t rays_fast;          // host-verified: every pixel's ray takes the Markstein path (tri_item FAST)
-  double o0, o1, o2;
-  int32_t num_pre;            // pcol (and prow in row_mode 2): split pair planes with numer, not d
-  int32_t pad_np;
-  const double* pcol;
-  int32_t n_pcol;
-  const double* prow;
-  int32_t n_prow;
-  double tol;
-  // outputs
-  void* xyz;
-  uint8_t* bgr;
-  int64_t* count;
-  WsHeader* ws;
-  uint64_t* states;        // [2][n_tiles]
-  int64_t n_tiles;
-  void* scratch_xyz;       // row_mode 2 row cloud
-  uint8_t* scratch_bgr;
-  int32_t dbg;             // env SLG_DBG; read only by the profiling instance (PROF): bit0 no
-                           // look-back wait, bit1 trivial triangulation, bit2 no output stores,
-                           // bit3 no BGR stores, bit6 per-workgroup phase records, bit7 no XYZ stores
-  uint32_t help_after;     // look-back: s_sleep(2) units before a silent predecessor is helped
-                           // (kHelpAfter; env SLG_HELP_AFTER=0 forces the helper path in tests)
-};
-
-// ------------------------------------------------------------------ decode (shared by the kernels)
-// Bit planes of 4 pixels accumulate one byte per pixel: plane b's compare mask (bit 7 of each
-// byte: pattern > inverse) enters at bit 7 while the earlier planes shift down, two VALU ops per
-// word per plane.  Planes 0-7 go to word A, planes 8-14 to word B.  After n planes, bit-reversing
-// the word (v_bfrev: bits within a byte AND the byte order) leaves pixel k's code MSB-first in
-// byte 3-k: A' byte = code >> m, B' byte = code & (2^m - 1), m = max(n - 8, 0).
-struct PlaneAcc {
-  uint32_t a[2], b[2];       // [pixels 0-3, 4-7]
-};
-
-__device__ inline void acc_plane(uint32_t& w, uint32_t m) { w = (w >> 1) | (m & 0x80808080u); }
-
-template <bool HI>
-__device__ inline void acc_pair(PlaneAcc& q, uint2 pv, uint2 iv) {
-  const uint32_t m0 = gt_u8x4(pv.x, iv.x);
-  const uint32_t m1 = gt_u8x4(pv.y, iv.y);
-  if (HI) { acc_plane(q.b[0], m0); acc_plane(q.b[1], m1); }
-  else { acc_plane(q.a[0], m0); acc_plane(q.a[1], m1); }
-}
-
-// The n-plane Gray codes of the lane's 8 pixels as two per word (16-bit halves), converted
-// like gray2bin_x2(code << pre) << post: w[2h] = pixels (4h, 4h+2) in (high, low) halves,
-// w[2h+1] = pixels (4h+1, 4h+3).
-__device__ inline void acc_codes(const PlaneAcc& q, int n, int pre, int post, uint32_t (&w)[4]) {
-  const int m = n > 8 ? n - 8 : 0;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const uint32_t A = __builtin_bitreverse32(q.a[h]), B = __builtin_bitreverse32(q.b[h]);
-    const uint32_t hi = (((A >> 8) & 0x00ff00ffu) << m) | ((B >> 8) & 0x00ff00ffu);
-    const uint32_t lo = ((A & 0x00ff00ffu) << m) | (B & 0x00ff00ffu);
-    w[2 * h] = gray2bin_x2(hi << pre) << post;
-    w[2 * h + 1] = gray2bin_x2(lo << pre) << post;
-  }
-}
-
-// code of pixel k (0..7) from acc_codes' words
-__device__ inline int unpack_code(const uint32_t (&w)[4], int k) {
-  const uint32_t a = w[((k >> 2) << 1) | (k & 1)];
-  return int((a >> (16 * (1 - ((k >> 1) & 1)))) & 0xffffu);
-}
-
-// 8 once-read bytes at base + off as a buffer load (scalar descriptor, 32-bit lane offset).
-__device__ inline uint2 ld_once8_buf(const uint8_t* base, uint32_t off) {
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(base), 0, 0xffffffff, 0x00020000);
-  const auto v = __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, SLG_NT_LOADS ? 2 : 0);   // aux 2: nt
-  return make_uint2(v[0], v[1]);
-}
-
-// A wave-uniform 64-bit value pinned to SGPRs: the compiler cannot fold a lane offset into it
-// first, so frame f's address is (frames + lane offset) + one scalar term -- one VALU add per
-// load instead of a 64-bit vector multiply-add.
-__device__ inline int64_t sgpr64(int64_t v) {
-  const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(uint64_t(v)));
-  const uint32_t hi = __builtin_amdgcn_readfirstlane(uint32_t(uint64_t(v) >> 32));
-  return int64_t((uint64_t(hi) << 32) | lo);
-}
-
-// 8 frame bytes at pixel lp (clamped in-bounds by the caller; rows are padded to >= 8 px).
-// As a buffer load: the frame's base lives in a scalar resource descriptor and the lane offset
-// is a 32-bit VGPR (buffer_load_dwordx2 ... offen nt), so the address costs no VALU at all.
-__device__ inline uint2 ld_frame8(const MainParams& p, int frame, int64_t lp) {
-#if SLG_FRAME_BUFFER_LOADS
-  // one descriptor for the whole stack, the frame's offset in the scalar soffset (a capture's
-  // frames span < 4 GiB: check_capture)
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(p.frames), 0, 0xffffffff, 0x00020000);
-  const auto v = __builtin_amdgcn_raw_buffer_load_b64(r, uint32_t(lp), uint32_t(frame) * uint32_t(p.stride),
-                                                      SLG_NT_LOADS ? 2 : 0);   // aux 2: nt
-  return make_uint2(v[0], v[1]);
-#else
-  return ld_once8(p.frames + sgpr64(int64_t(frame) * p.stride) + uint32_t(lp));
-#endif
-}
-
-// Paired 16-byte frame loads (two-axis decodes): lanes 2j and 2j+1 own pixels [q, q + 16) of the
-// tile (q = the even lane's px0, a multiple of 16).  For a frame pair (a, a + 1) -- white / black,
-// or a pattern / inverse pair -- the even lane reads 16 bytes of frame a and the odd lane 16 bytes
-// of frame a + 1 at q, then the two trade halves (DPP quad_perm [1,0,3,2]), so each holds its own
-// 8 pixels of both frames.  Half the vector-memory instructions of two 8-byte loads per lane and
-// the same 128-byte lines (tools/fetch_probe.hip: C2's mask-gated reads 11.1 vs 12.1-12.4 us;
-// the bench's C2 step 305.5 vs 309.8 us, f64 neutral, profiles/r7l).  Pairing the texture and the
-// carried white / black loads too measured slower or neutral (306.2 / 310.6 us; as buffer loads
-// 311.2 vs 310.5, profiles/r7l).  An unaligned caller stack keeps the 8-byte loads (GPU test).
-// Needs 16-byte aligned frames and stride (else the 8-byte loads run) and both lanes of a pair
-// active at the trade.
-
-struct PairLd {
-  uint32_t v[4];
-};
-__device__ inline PairLd ld_pair16(const MainParams& p, int frame_a, uint32_t voff) {
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(p.frames), 0, 0xffffffff, 0x00020000);
-  const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, uint32_t(frame_a) * uint32_t(p.stride),
-                                                       SLG_NT_LOADS ? 2 : 0);   // aux 2: nt
-  return {{v[0], v[1], v[2], v[3]}};
-}
-// a = this lane's 8 bytes of frame a, b = of frame a + 1
-__device__ inline void pair_split(const PairLd& L, bool odd, uint2& a, uint2& b) {
-  const uint32_t s0 = odd ? L.v[0] : L.v[2], s1 = odd ? L.v[1] : L.v[3];
-  const uint32_t r0 = uint32_t(__builtin_amdgcn_update_dpp(0, int(s0), 0xB1, 0xf, 0xf, false));   // quad_perm [1,0,3,2]
-  const uint32_t r1 = uint32_t(__builtin_amdgcn_update_dpp(0, int(s1), 0xB1, 0xf, 0xf, false));
-  a = odd ? make_uint2(r0, r1) : make_uint2(L.v[0], L.v[1]);
-  b = odd ? make_uint2(L.v[2], L.v[3]) : make_uint2(r0, r1);
-}
-
-// Decode the 8 pixels of one lane: mask bits + column / row codes.  Frame loads of both axes
-// are issued up to kBatch pairs at a time before any is consumed (memory-level parallelism).
-// `tail` (wave-uniform) is set only in the last tile, where map/texture reads need guards;
-// frame reads never do: the frame stride is >= round_up(H*W, 8) and out-of-image lanes read
-// pixel 0 (their mask bits are cleared).
-// MF (mask first, the fused reconstruction only): the mask is computed from white / black before
-// any pattern frame is read, and a lane none of whose 8 pixels is valid reads no pattern frame at
-// all (its codes are never used: the reference masks them out, processing.py:121-124,157).  The
-// memory system then fetches only the 64-byte segments a valid pixel lies in.  `pre()` runs once
-// the lane is known to hold a valid pixel, before its pattern loads (the texture loads).
-struct NoPre {
-  __device__ void operator()(uint2) const {}
-};
-
-// PLAN: (col_pairs << 4) | row_pairs as compile-time constants (main3's specialised instances for
-// the common capture layouts, SLG_PLAN_*; every view of such a launch has that plan), or 0: the
-// counts come from the view's plan at run time.
-// Constant counts make every frame load unconditional, so the decode consumes each pair as it
-// lands (vmcnt(n) in issue order) instead of after a vmcnt(0) for the whole batch, and drop the
-// per-pair branches (243.3 vs 259.8 us per 12-view launch, profiles/r3m).
-template <int ROW_MODE, int SRC_FRAMES, int kBatch, bool MF = false, int PLAN = 0, class Pre = NoPre>
-__device__ inline void decode_lane(const MainParams& p, int64_t px0, bool tail, uint32_t& valid,
-                                   int (&col)[kPx], int (&row)[kPx], Pre pre = Pre()) {
-  valid = 0;
-  if (SRC_FRAMES) {
-    const int smin = p.ws->smin, cmin = p.ws->cmin;
-    const int64_t lp = px0 < p.n_px ? px0 : 0;
-    // paired 16-byte loads (wave-uniform choice): the pair's base pixel, clamped like lp
-    // (column-only decodes -- row_mode 0, C1's 10 pairs -- measured 2-5 % slower paired: there the
-    // lanes a partner drags into the decode cost more than the halved loads save)
-    const bool paired = ROW_MODE != 0 &&
-                        ((reinterpret_cast<uintptr_t>(p.frames) | uint64_t(p.stride)) & 15) == 0;
-    const bool odd = (threadIdx.x & 1) != 0;
-    const int64_t q = px0 & ~int64_t(15);
-    const uint32_t vo = uint32_t(q < p.n_px ? q : 0) + (odd ? uint32_t(p.stride) : 0u);
-    uint2 w, bl;
-    if (paired) pair_split(ld_pair16(p, 0, vo), odd, w, bl);
-    else { w = ld_frame8(p, 0, lp); bl = ld_frame8(p, 1, lp); }
-    if constexpr (MF) {
-#pragma unroll
-      for (int k = 0; k < kPx; ++k) {
-        const int wv = ((k < 4 ? w.x : w.y) >> (8 * (k & 3))) & 0xff;
-        const int bv = ((k < 4 ? bl.x : bl.y) >> (8 * (k & 3))) & 0xff;
-        valid |= uint32_t((wv >= smin) & ((wv - bv) >= cmin) & (px0 + k < p.n_px)) << k;
-        col[k] = 0;
-        row[k] = 0;
-      }
-      // paired: a pair reads its pattern frames if either lane has a valid pixel (both must
-      // take part in the trades); the other lane's codes are never used
-      const uint32_t go = paired ? (valid | uint32_t(__builtin_amdgcn_update_dpp(0, int(valid), 0xB1, 0xf, 0xf, false)))
-                                 : valid;
-      if (go == 0u) return;
-      if (valid != 0u) pre(w);                    // (white bytes: a gray capture's texture)
-    }
-    PlaneAcc qc = {{0, 0}, {0, 0}}, qr = {{0, 0}, {0, 0}};
-    const int np_c = PLAN ? ((PLAN >> 4) & 15) : p.plan.col_pairs;
-    const int np_r = ROW_MODE == 0 ? 0 : (PLAN ? (PLAN & 15) : p.plan.row_pairs);
-    // compile-time trip count (kMaxBits pairs max), fully unrolled: only forward, wave-uniform
-    // branches remain, so the loads of a batch stay in flight together (no vmcnt(0) per load)
-    if (paired) {
-#pragma unroll
-      for (int b0 = 0; b0 < kMaxBits; b0 += kBatch) {
-        PairLd cl[kBatch], rl[kBatch];
-#pragma unroll
-        for (int g = 0; g < kBatch; ++g)
-          if (b0 + g < np_c) cl[g] = ld_pair16(p, p.plan.col_first + 2 * (b0 + g), vo);
-#pragma unroll
-        for (int g = 0; g < kBatch; ++g)
-          if (b0 + g < np_r) rl[g] = ld_pair16(p, p.plan.row_first + 2 * (b0 + g), vo);
-#pragma unroll
-        for (int g = 0; g < kBatch; ++g)
-          if (b0 + g < np_c) {
-            uint2 pv, iv;
-            pair_split(cl[g], odd, pv, iv);
-            if (b0 + g < 8) acc_pair<false>(qc, pv, iv);
-            else acc_pair<true>(qc, pv, iv);
-          }
-#pragma unroll
-        for (int g = 0; g < kBatch; ++g)
-          if (b0 + g < np_r) {
-            uint2 pv, iv;
-            pair_split(rl[g], odd, pv, iv);
-            if (b0 + g < 8) acc_pair<false>(qr, pv, iv);
-            else acc_pair<true>(qr, pv, iv);
-          }
-      }
-    } else {
-#pragma unroll
-    for (int b0 = 0; b0 < kMaxBits; b0 += kBatch) {
-      uint2 cp[kBatch], ci[kBatch], rp[kBatch], ri[kBatch];
-#pragma unroll
-      for (int g = 0; g < kBatch; ++g)
-        if (b0 + g < np_c) {
-          cp[g] = ld_frame8(p, p.plan.col_first + 2 * (b0 + g), lp);
-          ci[g] = ld_frame8(p, p.plan.col_first + 2 * (b0 + g) + 1, lp);
-        }
-#pragma unroll
-      for (int g = 0; g < kBatch; ++g)
-        if (b0 + g < np_r) {
-          rp[g] = ld_frame8(p, p.plan.row_first + 2 * (b0 + g), lp);
-          ri[g] = ld_frame8(p, p.plan.row_first + 2 * (b0 + g) + 1, lp);
-        }
-#pragma unroll
-      for (int g = 0; g < kBatch; ++g)
-        if (b0 + g < np_c) {
-          if (b0 + g < 8) acc_pair<false>(qc, cp[g], ci[g]);
-          else acc_pair<true>(qc, cp[g], ci[g]);
-        }
-#pragma unroll
-      for (int g = 0; g < kBatch; ++g)
-        if (b0 + g < np_r) {
-          if (b0 + g < 8) acc_pair<false>(qr, rp[g], ri[g]);
-          else acc_pair<true>(qr, rp[g], ri[g]);
-        }
-    }
-    }
-    uint32_t ac[4], ar[4];
-    acc_codes(qc, np_c, p.plan.col_pre, p.plan.col_post, ac);
-    acc_codes(qr, np_r, p.plan.row_pre, p.plan.row_post, ar);
-#pragma unroll
-    for (int k = 0; k < kPx; ++k) {
-      if constexpr (!MF) {
-        const int wv = ((k < 4 ? w.x : w.y) >> (8 * (k & 3))) & 0xff;
-        const int bv = ((k < 4 ? bl.x : bl.y) >> (8 * (k & 3))) & 0xff;
-        valid |= uint32_t((wv >= smin) & ((wv - bv) >= cmin) & (px0 + k < p.n_px)) << k;
-      }
-      col[k] = unpack_code(ac, k);
-      row[k] = ROW_MODE != 0 ? unpack_code(ar, k) : 0;
-    }
-  } else {
-    if (!tail) {
-      const uint2 mv = *reinterpret_cast<const uint2*>(p.in_mask + px0);
-      const int4* ic = reinterpret_cast<const int4*>(p.in_col + px0);
-      const int4 c0 = ic[0], c1 = ic[1];
-      col[0] = c0.x; col[1] = c0.y; col[2] = c0.z; col[3] = c0.w;
-      col[4] = c1.x; col[5] = c1.y; col[6] = c1.z; col[7] = c1.w;
-      if constexpr (ROW_MODE != 0) {
-        const int4* ir = reinterpret_cast<const int4*>(p.in_row + px0);
-        const int4 r0 = ir[0], r1 = ir[1];
-        row[0] = r0.x; row[1] = r0.y; row[2] = r0.z; row[3] = r0.w;
-        row[4] = r1.x; row[5] = r1.y; row[6] = r1.z; row[7] = r1.w;
-      } else {
-#pragma unroll
-        for (int k = 0; k < kPx; ++k) row[k] = 0;
-      }
-#pragma unroll
-      for (int k = 0; k < kPx; ++k) valid |= uint32_t((((k < 4 ? mv.x : mv.y) >> (8 * (k & 3))) & 0xff) != 0) << k;
-    } else {
-#pragma unroll
-      for (int k = 0; k < kPx; ++k) {
-        const bool in = px0 + k < p.n_px;
-        col[k] = in ? p.in_col[px0 + k] : 0;
-        row[k] = (in && ROW_MODE != 0) ? p.in_row[px0 + k] : 0;
-        valid |= uint32_t(in && p.in_mask[px0 + k] != 0) << k;
-      }
-    }
-  }
-}
-
-// clamp like np.clip(idx, 0, n-1) (processing.py:159,189) and pack col | row << 16
-template <int ROW_MODE>
-__device__ inline uint32_t pack_code(const MainParams& p, int c, int r) {
-  c = c < 0 ? 0 : (c > p.n_pcol - 1 ? p.n_pcol - 1 : c);
-  r = ROW_MODE == 0 ? 0 : (r < 0 ? 0 : (r > p.n_prow - 1 ? p.n_prow - 1 : r));
-  return uint32_t(c) | (uint32_t(r) << 16);
-}
-
-struct TriOut {
-  double x, y, z;      // column-stream point (row_mode 0/1), or column point (row_mode 2)
-  double rx, ry, rz;   // row-stream point (row_mode 2)
-  double t, tr;        // their ray parameters: (x, y, z) = Oc + r * t, (rx, ry, rz) = Oc + r * tr
-  uint32_t keep;       // bit 0 column stream, bit 1 row stream
-};
-
-// Ray-plane intersection of one valid pixel (processing.py:143-234), fp64 in NumPy's order, in
-// three parts so phase B can issue an item's plane gathers, compute its ray while they are in
-// flight, and only then combine (tri_item chains them for the other callers).
-struct TriPlanes {
-  double2 pc01, pc23;  // column plane: (n0, n1), (n2, d or numer)
-  double2 pr01, pr23;  // row plane (row_mode 1/2)
-};
-
-// Plane rows: (n0, n1, n2, d) row-major, or -- with the precomputed-numerator tables -- split
-// in pair planes [0][c] = (n0, n1), [1][c] = (n2, numer): a wave's consecutive column codes
-// then read consecutive 16-byte pairs (8 per cache line) instead of every other 16 bytes of
-// 32-byte rows.
-// NP: 0 reads p.num_pre at run time, 1 / 2 take it as set / clear (phase B picks per workgroup).
-template <int NP = 0>
-__device__ inline void tri_planes_col(const MainParams& p, uint32_t code, double2& pc01, double2& pc23) {
-  if (NP == 1 || (NP == 0 && p.num_pre)) {
-    const double2* qc = reinterpret_cast<const double2*>(p.pcol);
-    const uint32_t cc = code & 0xffffu;
-    pc01 = qc[cc];
-    pc23 = qc[p.n_pcol + cc];
-  } else {
-    const double2* qc = reinterpret_cast<const double2*>(p.pcol + 4 * int64_t(code & 0xffffu));
-    pc01 = qc[0];
-    pc23 = qc[1];
-  }
-}
-
-template <int ROW_MODE, int NP = 0>
-__device__ inline void tri_planes_row(const MainParams& p, uint32_t code, double2& pr01, double2& pr23) {
-  pr01 = make_double2(0, 0);
-  pr23 = make_double2(0, 0);
-  if constexpr (ROW_MODE == 2) {
-    if (NP == 1 || (NP == 0 && p.num_pre)) {
-      const double2* qr = reinterpret_cast<const double2*>(p.prow);
-      pr01 = qr[code >> 16];
-      pr23 = qr[p.n_prow + (code >> 16)];
-    } else {
-      const double2* qr = reinterpret_cast<const double2*>(p.prow + 4 * int64_t(code >> 16));
-      pr01 = qr[0];
-      pr23 = qr[1];
-    }
-  } else if constexpr (ROW_MODE != 0) {
-    const double2* qr = reinterpret_cast<const double2*>(p.prow + 4 * int64_t(code >> 16));
-    pr01 = qr[0];
-    pr23 = qr[1];
-  }
-}
-
-template <int ROW_MODE, int NP = 0>
-__device__ inline TriPlanes tri_planes(const MainParams& p, uint32_t code) {
-  TriPlanes t;
-  tri_planes_col<NP>(p, code, t.pc01, t.pc23);
-  tri_planes_row<ROW_MODE, NP>(p, code, t.pr01, t.pr23);
-  return t;
-}
-
-
-// sqrt and 1/x of a double in [1, 2^900): the same fma sequences the compiler's IEEE-correct
-// expansions run (v_rsq_f64 + two Newton/correction rounds; v_rcp_f64 + two Newton rounds +
-// one correction, as v_div_scale/v_div_fmas/v_div_fixup compute them when nothing needs
-// scaling), without the range scaling and special-case selects that cannot trigger here: the
-// same bits, 11 fewer VALU instructions per pixel.
-__device__ inline double sqrt_ge1(double x) {
-  const double g = __builtin_amdgcn_rsq(x);
-  double s = x * g, h = g * 0.5;
-  const double r = __builtin_fma(-h, s, 0.5);
-  s = __builtin_fma(s, r, s);
-  double d = __builtin_fma(-s, s, x);
-  h = __builtin_fma(h, r, h);
-  s = __builtin_fma(d, h, s);
-  d = __builtin_fma(-s, s, x);
-  return __builtin_fma(d, h, s);
-}
-
-__device__ inline double rcp_ge1(double n) {
-  double y = __builtin_amdgcn_rcp(n);
-  y = __builtin_fma(y, __builtin_fma(-n, y, 1.0), y);
-  y = __builtin_fma(y, __builtin_fma(-n, y, 1.0), y);
-  return __builtin_fma(__builtin_fma(-n, y, 1.0), y, y);
-}
-
-// The pixel's unit ray (processing.py:143-156).  FAST (p.rays_fast, checked on the host for
-// every column and row of the image): the Markstein conditions hold for every pixel, so the
-// code is one straight-line block with no per-lane fallback branches -- the same values.
-template <int RAYS, bool FAST = false>
-__device__ inline void tri_ray(const MainParams& p, int u, int v, double& r0, double& r1, double& r2) {
-  if (RAYS == SLG_RAYS_PINHOLE) {
-    // The same IEEE quotients as the reference, with the divisions by fx, fy (per camera)
-    // and by the norm (three per pixel) done as Markstein corrections of one reciprocal.
-    // (Per-column / per-row tables of x and y measured 8 % slower: two more L2 gathers per
-    // point cost more than the fp64 they replace.)
-    const double ax = double(u) - p.cx, ay = double(v) - p.cy;
-    double x, y;
-    if constexpr (FAST) {
-      x = div_rn(ax, p.fx, p.rfx);                         // processing.py:150
-      y = div_rn(ay, p.fy, p.rfy);                         // processing.py:151
-    } else {
-      x = p.div_fast && div_rn_ok(ax) ? div_rn(ax, p.fx, p.rfx) : ax / p.fx;
-      y = p.div_fast && div_rn_ok(ay) ? div_rn(ay, p.fy, p.rfy) : ay / p.fy;
-    }
-    // np.linalg.norm(rays, axis=0), then rays /= norms; FAST: n in [1, 2^450) (host check)
-    const double s2 = (x * x + y * y) + 1.0;
-    const double n = FAST ? sqrt_ge1(s2) : sqrt(s2);
-    r2 = FAST ? rcp_ge1(n) : 1.0 / n;
-    if (FAST || (n < 0x1p900 && div_rn_ok(x) && div_rn_ok(y))) {   // n >= 1: its reciprocal is normal
-      r0 = div_rn(x, n, r2); r1 = div_rn(y, n, r2);
-    } else {
-      r0 = x / n; r1 = y / n;
-    }
-  } else {
-    const int64_t px = int64_t(v) * p.width + u;
-    r0 = p.rays[px]; r1 = p.rays[p.n_px + px]; r2 = p.rays[2 * p.n_px + px];
-  }
-}
-
-template <int ROW_MODE, bool FAST = false, int NP = 0>
-__device__ inline TriOut tri_combine(const MainParams& p, const TriPlanes& pl, double r0, double r1, double r2) {
-  const bool num_pre = NP == 1 || (NP == 0 && p.num_pre);
-  const double2 pc01 = pl.pc01, pc23 = pl.pc23, pr01 = pl.pr01, pr23 = pl.pr23;
-  TriOut o;
-  const double den = (pc01.x * r0 + pc01.y * r1) + pc23.x * r2;          // np.sum(N*rays, 0)
-  // numer = n.Oc + d (processing.py:163-165): precomputed per plane by the caller (column 3 of
-  // the table) or computed here
-  const double num = num_pre ? pc23.y : ((pc01.x * p.o0 + pc01.y * p.o1) + pc23.x * p.o2) + pc23.y;
-  const bool okc = fabs(den) > 1e-6;
-  double t;
-  if constexpr (FAST) {
-    const double q = (-num) / den;                         // unconditional: a select, not a branch
-    t = okc ? q : 0.0;
-  } else {
-    t = okc ? (-num) / den : 0.0;
-  }
-  o.x = p.o0 + r0 * t; o.y = p.o1 + r1 * t; o.z = p.o2 + r2 * t;
-  o.t = t;
-  o.tr = 0.0;
-  o.keep = okc;
-  o.rx = o.ry = o.rz = 0.0;
-  if constexpr (ROW_MODE == 1) {                          // epipolar filter, processing.py:197-201
-    const double dist = fabs(((pr01.x * o.x + pr01.y * o.y) + pr23.x * o.z) + pr23.y);
-    o.keep = okc && (dist < p.tol);
-  }
-  if constexpr (ROW_MODE == 2) {                          // independent row cloud, :218-228
-    const double dr = (pr01.x * r0 + pr01.y * r1) + pr23.x * r2;
-    const double nr = num_pre ? pr23.y : ((pr01.x * p.o0 + pr01.y * p.o1) + pr23.x * p.o2) + pr23.y;
-    const bool okr = fabs(dr) > 1e-6;
-    double tr;
-    if constexpr (FAST) {
-      const double q = (-nr) / dr;
-      tr = okr ? q : 0.0;
-    } else {
-      tr = okr ? (-nr) / dr : 0.0;
-    }
-    o.rx = p.o0 + r0 * tr; o.ry = p.o1 + r1 * tr; o.rz = p.o2 + r2 * tr;
-    o.tr = tr;
-    o.keep |= uint32_t(okr) << 1;
-  }
-  return o;
-}
-
-template <int ROW_MODE, int RAYS, bool FAST = false>
-__device__ inline TriOut tri_item(const MainParams& p, uint32_t code, int u, int v) {
-  const TriPlanes pl = tri_planes<ROW_MODE>(p, code);
-  double r0, r1, r2;
-  tri_ray<RAYS, FAST>(p, u, v, r0, r1, r2);
-  return tri_combine<ROW_MODE, FAST>(p, pl, r0, r1, r2);
-}
-
-// One pixel decoded exactly as decode_lane decodes it, with byte loads and few registers
-// (the look-back helper path only).
-template <int ROW_MODE, int SRC_FRAMES>
-__device__ inline bool decode_px(const MainParams& p, int64_t px, int& col, int& row) {
-  if (SRC_FRAMES) {
-    const uint8_t* f = p.frames + px;
-    const int wv = f[0], bv = f[p.stride];
-    uint32_t c = 0, r = 0;
-    for (int b = 0; b < p.plan.col_pairs; ++b)
-      c = (c << 1) | uint32_t(f[int64_t(p.plan.col_first + 2 * b) * p.stride] > f[int64_t(p.plan.col_first + 2 * b + 1) * p.stride]);
-    col = int(gray2bin_x2(c << p.plan.col_pre) << p.plan.col_post);
-    if (ROW_MODE != 0) {
-      for (int b = 0; b < p.plan.row_pairs; ++b)
-        r = (r << 1) | uint32_t(f[int64_t(p.plan.row_first + 2 * b) * p.stride] > f[int64_t(p.plan.row_first + 2 * b + 1) * p.stride]);
-      r = gray2bin_x2(r << p.plan.row_pre) << p.plan.row_post;
-    }
-    row = int(r);
-    return (wv >= p.ws->smin) & ((wv - bv) >= p.ws->cmin);
-  }
-  col = p.in_col[px];
-  row = ROW_MODE != 0 ? p.in_row[px] : 0;
-  return p.in_mask[px] != 0;
-}
-
-// Keep-count of another tile of the same view, computed by the calling wave alone: the
-// aggregate a predecessor that has not published for a long time would publish (it may not
-// have been dispatched yet).  Same arithmetic as main3's phases A/B => same value.
-template <int ROW_MODE, int SRC_FRAMES, int RAYS>
-__device__ int tile_keep_count_wave(const MainParams& p, int tile, int stream) {
-  const int lane = threadIdx.x & 63;
-  int cnt = 0;
-  const int64_t tile_px = int64_t(tile) * kTilePx;
-#pragma unroll 1
-  for (int i = lane; i < kTilePx; i += 64) {
-    const int64_t px = tile_px + i;
-    int col, row;
-    if (px < p.n_px && decode_px<ROW_MODE, SRC_FRAMES>(p, px, col, row)) {
-      const int v = int(px / p.width), u = int(px - int64_t(v) * p.width);
-      const TriOut o = tri_item<ROW_MODE, RAYS>(p, pack_code<ROW_MODE>(p, col, row), u, v);
-      cnt += (o.keep >> stream) & 1u;
-    }
-  }
-  return wave_sum(cnt);
-}
-
-__device__ inline void publish_agg(uint64_t* w, int agg) {   // unless a helper already did
-  unsigned long long expect = 0;
-  __hip_atomic_compare_exchange_strong(reinterpret_cast<unsigned long long*>(w), &expect,
-                                       (unsigned long long)(kFlagAgg | uint64_t(agg)), __ATOMIC_RELAXED,
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-constexpr unsigned kNapCap = 8;         // back-off cap: 8 x s_sleep(2) ~ 1k clocks between re-polls
-constexpr unsigned kHelpAfter = 2048;   // s_sleep(2) units (~0.1 ms) before asking for help
-
-// Look-back words st[b .. b+7] read by one scalar load that misses the scalar cache (glc): the
-// poll goes to L2 without queueing behind the co-resident workgroup's frame stream in the
-// CU's vector-memory pipeline (a vector poll waits behind up to ~180 KB of streaming loads).
-__device__ inline void ld_state8_scalar(const uint64_t* p, uint64_t (&v)[8]) {
-  typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
-  u32x16 r;
-  const uint64_t a = reinterpret_cast<uint64_t>(p);   // uniform: pinned to SGPRs for the "s" operand
-  const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(a));          // (the builtin returns int:
-  const uint32_t hi = __builtin_amdgcn_readfirstlane(uint32_t(a >> 32));    //  widen only as uint32)
-  const uint64_t sa = (uint64_t(hi) << 32) | lo;
-  asm volatile("s_load_dwordx16 %0, %1, 0x0 glc\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(sa) : "memory");
-#pragma unroll
-  for (int k = 0; k < 8; ++k) v[k] = uint64_t(r[2 * k]) | (uint64_t(r[2 * k + 1]) << 32);
-}
-
-// Decoupled look-back over static tile ids (wave 0 calls it, lane 0 publishes).  Returns true
-// with the exclusive prefix of `agg` over the view's tiles before `tile`, or false with the
-// nearest predecessor that has not published for p.help_after (it may not be dispatched yet:
-// dispatch order is not guaranteed): the caller then computes that tile's aggregate itself
-// (tile_keep_count_wave) and retries, so waiting always ends.  Polled 8 predecessors at a time
-// with wave-uniform scalar loads, newest first: aggregates are summed as they appear and the
-// walk stops at the first inclusive prefix; an unpublished entry is re-polled after a capped
-// back-off.  Published values never change (0 -> aggregate -> inclusive), so a stale read only
-// delays the walk, never changes the sum.
-template <bool PROF>
-__device__ bool lookback_scalar(const MainParams& p, uint64_t* st, int tile, int agg, bool published,
-                                uint64_t& excl_out, int& help_tile, uint32_t& polls, uint32_t& naps) {
-  const int lane = threadIdx.x & 63;
-  if (PROF && (p.dbg & 1)) { excl_out = uint64_t(tile) * kTilePx; return true; }   // ablation: no wait
-  if (tile == 0) {
-    if (lane == 0 && !published) st_state(&st[0], kFlagInc | uint64_t(agg));
-    excl_out = 0;
-    return true;
-  }
-  if (lane == 0 && !published) st_state(&st[tile], kFlagAgg | uint64_t(agg));
-  uint64_t excl = 0;
-  int j = tile - 1;                          // newest predecessor not summed yet
-  unsigned slept = 0, nap = 1;
-  for (;;) {
-    ++polls;
-    const int b = j >= 7 ? j - 7 : 0;
-    uint64_t v[8];
-    ld_state8_scalar(st + b, v);
-    bool done = false, stall = false;
-#pragma unroll
-    for (int k = 7; k >= 0; --k) {
-      if (done || stall || b + k > j) continue;
-      const uint64_t f = v[k] >> 62;
-      if (f == 0) { stall = true; continue; }
-      excl += v[k] & kValMask;
-      j = b + k - 1;
-      done = f == 2;
-    }
-    if (done || j < 0) break;
-    if (stall) {
-      if (slept >= p.help_after) {
-        help_tile = j;
-        return false;
-      }
-      for (unsigned z = 0; z < nap; ++z) __builtin_amdgcn_s_sleep(2);
-      slept += nap;
-      naps += nap;
-      nap = nap < kNapCap ? nap * 2 : kNapCap;
-    }
-  }
-  if (lane == 0) st_state(&st[tile], kFlagInc | (excl + uint64_t(agg)));
-  excl_out = excl;
-  return true;
-}
-
-// Publishes this tile's aggregate (tile 0: its inclusive prefix) and takes a ticket.  The last of
-// the view's tiles to do so finds every tile's word published: it scans them all, 8 consecutive
-// tiles per lane (a segmented scan: an inclusive word restarts the running sum), publishes every
-// tile's inclusive prefix, and returns true with its own exclusive prefix.  The others return
-// false and walk back (lookback_scalar) as before; a walk that is still polling when the scan
-// lands meets an inclusive prefix at its next poll.  A lone view's launch has every tile in
-// flight at once, so without the scan its walks are ~6.7 polls of ~0.8 us each
-// (profiles/r7w).  The values written are the ones the walks compute, so a word only ever
-// goes 0 -> aggregate -> inclusive prefix, whichever writer gets there first.
-constexpr int kScanPer = 8;                // lookback_scan: consecutive tiles per lane
-constexpr int kScanTiles = 2 * 64 * kScanPer;   // lone views up to 1024 tiles (4.2 MP) take the scan
-template <bool PROF>
-__device__ bool lookback_scan(const MainParams& p, uint64_t* st, int tile, int tiles, int agg, uint32_t* ticket,
-                              uint64_t& excl_out) {
-  const int lane = threadIdx.x & 63;
-  if (PROF && (p.dbg & 1)) return false;     // ablation (lookback_scalar): no wait
-  // (no release / acquire fences: on gfx950 an agent-scope one writes back or invalidates the
-  // L2 -- the bench shape took 716 instead of 313 us per step with them.  The words and the
-  // ticket are agent-scope atomics, performed at the L2 that owns the address, and the ticket is
-  // taken after vmcnt(0): the hardware assumption of stats_kernel's ticket)
-  uint32_t t = 0;
-  if (lane == 0) {
-    st_state(&st[tile], (tile == 0 ? kFlagInc : kFlagAgg) | uint64_t(agg));
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  t = __builtin_amdgcn_readfirstlane(t);
-  if (t != uint32_t(tiles - 1)) return false;
-  // kScanPer consecutive tiles per lane: their words loaded at once, summed in the lane, then one
-  // wave-wide segmented scan of the lane totals; blocks of 64 * kScanPer tiles in order
-  uint64_t carry = 0, mine = 0;
-  for (int c0 = 0; c0 < tiles; c0 += 64 * kScanPer) {
-    const int i0 = c0 + kScanPer * lane;
-    uint64_t w[kScanPer];
-#pragma unroll
-    for (int k = 0; k < kScanPer; ++k) w[k] = i0 + k < tiles ? ld_state(&st[i0 + k]) : 0;
-    uint64_t x = 0;                          // the lane's running segmented sum
-    bool f = false;                          // an inclusive word seen in the lane so far
-#pragma unroll
-    for (int k = 0; k < kScanPer; ++k) {
-      const bool inc = (w[k] >> 62) == 2;
-      x = inc ? (w[k] & kValMask) : x + (w[k] & kValMask);
-      f = f || inc;
-    }
-    uint64_t sx = x;                         // inclusive segmented scan of the lane totals
-    bool sf = f;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint64_t xo = __shfl_up(sx, o);
-      const bool fo = __shfl_up(int(sf), o) != 0;
-      if (lane >= o && !sf) { sx += xo; sf = fo; }
-    }
-    uint64_t ex = __shfl_up(sx, 1);          // the lanes before this one (+ carry unless they hold
-    const bool ef = lane > 0 && __shfl_up(int(sf), 1) != 0;   //  an inclusive word)
-    ex = (lane == 0 ? 0 : ex) + (ef ? 0 : carry);
-    x = ex;
-#pragma unroll
-    for (int k = 0; k < kScanPer; ++k) {
-      const bool inc = (w[k] >> 62) == 2;
-      x = inc ? (w[k] & kValMask) : x + (w[k] & kValMask);
-      if (i0 + k < tiles && !inc) st_state(&st[i0 + k], kFlagInc | x);
-      if (i0 + k == tile) mine = x;
-    }
-    carry = __shfl(x, 63);
-  }
-  mine = __builtin_amdgcn_readlane(uint32_t(mine), (tile % (64 * kScanPer)) / kScanPer) |
-         (uint64_t(__builtin_amdgcn_readlane(uint32_t(mine >> 32), (tile % (64 * kScanPer)) / kScanPer)) << 32);
-  excl_out = mine - uint64_t(agg);
-  return true;
-}
 
 // Correspondence maps of 2048 pixels per workgroup (slg_decode): col/row int32, mask uint8.
 // (Plan-specialised instances as main3's measured the same: 21.3 vs 21.4 us at 1080p, r3an2.)
@@ -1041,146 +97,18 @@ __global__ __launch_bounds__(kBlock) void decode_maps_kernel(MainParams p) {
 //     points, so the compacted stores coalesce without an LDS staging copy.
 // 49 KB of LDS (24 KB at 256 lanes) and no point staging keep two 512-lane workgroups per CU
 // resident, so one tile's decode stream overlaps another's fp64 work and look-back.
-constexpr int kMaxViews = 16;
 #ifndef SLG_DECODE_BATCH
 #define SLG_DECODE_BATCH 11                // pairs per axis in flight per lane (4/6/8/11: 31.7/30.3/28.7/27.5 us/view)
-#endif
-#ifndef SLG_TRI_GROUP
-#define SLG_TRI_GROUP 4                    // phase B: rounds (items per lane) whose gathers are in flight together
 #endif
 #ifndef SLG_M3_WAVES
 #define SLG_M3_WAVES 4                     // waves per SIMD main3 is register-budgeted for
 #endif
-
-struct ViewIO {
-  const uint8_t* frames;      // SRC_FRAMES: [F][stride]
-  const uint8_t* texture;     // [n_px][3] BGR
-  const int32_t* in_col;      // !SRC_FRAMES: maps
-  const int32_t* in_row;
-  const uint8_t* in_mask;
-  void* xyz;
-  uint8_t* bgr;
-  int64_t* count;
-  WsHeader* ws;
-  uint64_t* states;           // [2][n_tiles]
-  void* scratch_xyz;          // row_mode 2 row cloud
-  uint8_t* scratch_bgr;
-  int64_t stride;             // frame stride of this view
-  Plan plan;                  // decode plan of this view (frames present)
-  const uint8_t* hn_white;    // batch after next: white / black of the view in this slot, whose
-  const uint8_t* hn_black;    // Otsu histograms this launch computes per tile (NULL: none)
-  uint32_t* hn_part;          // -> [n_tiles][kPartWords] of this view's workspace slice
-};
-
-// A view whose Otsu partials (carried by an EARLIER launch on the same stream) this launch
-// turns into thresholds, with finishing workgroups placed at the front of its grid: the
-// streaming pipeline's stats pass then costs no kernel and no cross-stream wait of its own.
-struct FinIO {
-  const uint32_t* parts;      // [n_tiles][kPartWords] partials in the view's workspace slice
-  WsHeader* ws;               // the slice: thresholds out, look-back words armed
-};
-
-struct Main3Params {
-  MainParams c;               // geometry, decode plan, calibration (per-view pointers unused)
-  int32_t n_views;
-  int32_t n_fin;              // views finished by this launch (FinIO), 0: none
-  int32_t fin_blocks;         // finishing workgroups per such view (the grid's first n_fin*fin_blocks)
-  int32_t pad_m3;
-  int64_t n_state_words;      // look-back words per view slice (finishing arms them)
-  int64_t pad_zero;           // zero bytes the last tile's partial counted past n_px
-  ViewIO v[kMaxViews];
-  FinIO fin[kMaxViews];
-};
-
-static_assert(sizeof(Main3Params) <= 4096, "kernel arguments");
-static_assert(sizeof(Plan) == 32 && offsetof(MainParams, plan) == 60 && offsetof(MainParams, out_col) == 96 &&
-              sizeof(MainParams) == 328 && offsetof(ViewIO, plan) == 104 && offsetof(ViewIO, hn_white) == 136 &&
-              sizeof(ViewIO) == 160, "kernel argument layout (Plan sits where its eight fields did)");
-
-__device__ inline MainParams view_params(const Main3Params& P, int view) {
-  MainParams q = P.c;
-  const ViewIO& io = P.v[view];
-  q.frames = io.frames; q.texture = io.texture;
-  q.in_col = io.in_col; q.in_row = io.in_row; q.in_mask = io.in_mask;
-  q.xyz = io.xyz; q.bgr = io.bgr; q.count = io.count;
-  q.ws = io.ws; q.states = io.states;
-  q.scratch_xyz = io.scratch_xyz; q.scratch_bgr = io.scratch_bgr;
-  q.stride = io.stride;
-  q.plan = io.plan;
-  return q;
-}
 
 // BGR bytes of pixel k (0..7) from the lane's 24 texture bytes t[0..5].
 __device__ inline uint32_t bgr_of(const uint32_t (&t)[6], int k) {
   const int b = 3 * k, w = b >> 2, s = 8 * (b & 3);
   const uint64_t pair = uint64_t(t[w]) | (uint64_t(w + 1 < 6 ? t[w + 1] : 0u) << 32);
   return uint32_t(pair >> s) & 0xffffffu;
-}
-
-// The Otsu histograms (white, clip(white - black)) of another capture over this tile's pixel
-// range, as u16 counts [2][256] packed in pairs (1 KB per tile) -- the stats pass of the batch
-// after next, carried by this fused launch (stats_kernel's partials mode sums the tiles).
-// Split so it costs neither latency nor chain time: the loads are issued when the workgroup
-// starts (hist_next_load), the nibble planes staged once the points are computed
-// (hist_next_stage), the matrix-core counting done by waves 1..3 while wave 0 runs the
-// look-back (hist_next_count, as mfma_hist_chunk) and the partial written after it
-// (hist_next_write).  Bytes past n_px count as 0 (pad_zero).
-__device__ inline void hist_next_load(const uint8_t* white, const uint8_t* black, int64_t n_px, int64_t o,
-                                      uint2& wq, uint2& bq) {
-  wq = make_uint2(0, 0);
-  bq = make_uint2(0, 0);
-  if (o < n_px) {                            // frames readable to round_up(n, 8)
-    wq = ld_once8_buf(white, uint32_t(o));     // o < n_px < 2^31
-    bq = ld_once8_buf(black, uint32_t(o));
-  }
-}
-
-// stage: [wave][hi_w, lo_w, hi_d, lo_d][64 lanes] uint2 (the lane's 8 pixels per plane)
-__device__ inline void hist_next_stage(uint2 wq, uint2 bq, int64_t n_px, int64_t o, uint2* stage) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (o + 8 > n_px) {                        // tail: zero the bytes at or past n_px
-    const uint64_t mk = o >= n_px ? 0ull : (~0ull >> (64 - 8 * (n_px - o)));
-    wq.x &= uint32_t(mk); wq.y &= uint32_t(mk >> 32);
-    bq.x &= uint32_t(mk); bq.y &= uint32_t(mk >> 32);
-  }
-  const uint32_t m4 = 0x0f0f0f0fu;
-  const uint32_t d0 = sub_sat_u8x4(wq.x, bq.x), d1 = sub_sat_u8x4(wq.y, bq.y);
-  uint2* st = stage + wave * 256;
-  st[lane] = make_uint2((wq.x >> 4) & m4, (wq.y >> 4) & m4);
-  st[64 + lane] = make_uint2(wq.x & m4, wq.y & m4);
-  st[128 + lane] = make_uint2((d0 >> 4) & m4, (d1 >> 4) & m4);
-  st[192 + lane] = make_uint2(d0 & m4, d1 & m4);
-}
-
-// Steps h, h + n_help, ... of the tile's kTilePx / 64 MFMA steps (64 pixels each), added to
-// s_h[512] (zeroed beforehand) with LDS atomics.
-__device__ inline void hist_next_count(const uint2* stage, uint32_t* s_h, int h, int n_help) {
-  const int lane = threadIdx.x & 63;
-  const uint32_t repx = (uint32_t(lane & 15) * 0x01010101u) ^ 0x0f0f0f0fu;
-  v4i32 acc_w = {0, 0, 0, 0}, acc_d = {0, 0, 0, 0};
-  for (int step = h; step < kTilePx / 64; step += n_help) {
-    const uint2* st = stage + (step >> 3) * 256 + 8 * (step & 7) + 2 * (lane >> 4);   // lanes src, src+1
-    const uint4 hw = *reinterpret_cast<const uint4*>(st);
-    const uint4 lw = *reinterpret_cast<const uint4*>(st + 64);
-    const uint4 hd = *reinterpret_cast<const uint4*>(st + 128);
-    const uint4 ld = *reinterpret_cast<const uint4*>(st + 192);
-    const v4i32 aw = {onehot16(hw.x, repx), onehot16(hw.y, repx), onehot16(hw.z, repx), onehot16(hw.w, repx)};
-    const v4i32 bw = {onehot16(lw.x, repx), onehot16(lw.y, repx), onehot16(lw.z, repx), onehot16(lw.w, repx)};
-    const v4i32 ad = {onehot16(hd.x, repx), onehot16(hd.y, repx), onehot16(hd.z, repx), onehot16(hd.w, repx)};
-    const v4i32 bd = {onehot16(ld.x, repx), onehot16(ld.y, repx), onehot16(ld.z, repx), onehot16(ld.w, repx)};
-    acc_w = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw, bw, acc_w, 0, 0, 0);
-    acc_d = __builtin_amdgcn_mfma_i32_16x16x64_i8(ad, bd, acc_d, 0, 0, 0);
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int bin = 16 * (4 * (lane >> 4) + r) + (lane & 15);
-    if (acc_w[r]) atomicAdd(&s_h[bin], uint32_t(acc_w[r]) >> 8);
-    if (acc_d[r]) atomicAdd(&s_h[256 + bin], uint32_t(acc_d[r]) >> 8);
-  }
-}
-
-__device__ inline void hist_next_write(const uint32_t* s_h, uint32_t* part) {
-  for (int i = threadIdx.x; i < kPartWords; i += kTileBlock) part[i] = s_h[2 * i] | (s_h[2 * i + 1] << 16);
 }
 
 // Block-wide exclusive scan of one int per lane: (exclusive prefix, block total).
@@ -1203,178 +131,9 @@ __device__ inline int2 block_scan(int x, int* s_wtot) {
   return make_int2(off + incl - x, tot);
 }
 
-// LDS slots of compacted item m: phase A writes lane L's items at m = prefix(L) + j, a stride of
-// up to 8 items between neighbouring lanes (16 words for the 8-byte records: 16 lanes per
-// bank); one pad slot per 16 records (per 8 BGR words) makes that stride odd in words.
-#ifndef SLG_ITEM_PAD
-#define SLG_ITEM_PAD 4                     // one pad record per 2^SLG_ITEM_PAD items
-#endif
-#ifndef SLG_BGR_PAD
-#define SLG_BGR_PAD 3                      // one pad word per 2^SLG_BGR_PAD BGR words
-#endif
-constexpr int kItemSlots = kTilePx + (kTilePx >> SLG_ITEM_PAD), kBgrSlots = kTilePx + (kTilePx >> SLG_BGR_PAD);
-__device__ inline int item_slot(int m) { return m + (m >> SLG_ITEM_PAD); }
-__device__ inline int bgr_slot(int m) { return m + (m >> SLG_BGR_PAD); }
-
 #ifndef SLG_X64_KEEP_T
 #define SLG_X64_KEEP_T 1                   // f64 XYZ, pinhole rays: t in registers, ray recomputed in phase D
 #endif
-// Phase B of main3 for rounds [i, i + G) (item m = tid + kTileBlock * round), FAST path: the G
-// items' loads and fp64 chains are independent, so their plane gathers are in flight together.
-// tri_rounds: i is a compile-time multiple of G (the unrolled group loop); tri_rounds_at: any i.
-// This is the grouped schedule (SLG_TRI_GROUP): the instances without static schedules run it
-// (row_mode 2 with f32 XYZ, or every instance of a -DSLG_TRI_STATIC=0 build); the others take
-// tri_rounds_static below.
-template <int G, int ROW_MODE, int RAYS, typename XT, int NS, int kIt, int NP = 0, int NC = 3>
-__device__ inline void tri_rounds_at(const MainParams& p, int i, int n_items, const uint2* s_item,
-                                     XT (&pts)[NS][kIt][NC], uint64_t (&km)[NS][kIt]) {
-  const int tid = threadIdx.x;
-  TriOut o[G];
-  TriPlanes pl[G];
-  double ra[G][3];
-  bool in[G];
-  uint32_t uvs[G];
-#pragma unroll
-  for (int h = 0; h < G; ++h) {                    // the G items' plane gathers, all in flight ...
-    const int m = tid + kTileBlock * (i + h);
-    in[h] = m < n_items;
-    const uint2 it = s_item[item_slot(m)];          // m < kTilePx; garbage past n_items masked
-    const uint32_t sc = it.x, suv = it.y;
-    const uint32_t code = in[h] ? sc : 0u;
-    uvs[h] = in[h] ? suv : 0u;
-    pl[h] = tri_planes<ROW_MODE, NP>(p, code);
-  }
-#pragma unroll
-  for (int h = 0; h < G; ++h)                      // ... while the rays are computed
-    tri_ray<RAYS, true>(p, int(uvs[h] & 0xffffu), int(uvs[h] >> 16), ra[h][0], ra[h][1], ra[h][2]);
-  __builtin_amdgcn_sched_barrier(0);               // keep the combine (first use of the planes) after them
-#pragma unroll
-  for (int h = 0; h < G; ++h) o[h] = tri_combine<ROW_MODE, true, NP>(p, pl[h], ra[h][0], ra[h][1], ra[h][2]);
-#pragma unroll
-  for (int h = 0; h < G; ++h) {
-    const uint32_t keep = in[h] ? o[h].keep : 0u;
-    // runtime round index: select into the register arrays (unrolled compares, no scratch)
-#pragma unroll
-    for (int r = 0; r < kIt; ++r)
-      if (r == i + h) {
-        if constexpr (NC == 1) {                   // the ray parameters only (x64_keep_t)
-          pts[0][r][0] = o[h].t;
-          if constexpr (ROW_MODE == 2) pts[NS - 1][r][0] = o[h].tr;
-        } else {
-          pts[0][r][0] = XT(o[h].x); pts[0][r][1] = XT(o[h].y); pts[0][r][2] = XT(o[h].z);
-          if constexpr (ROW_MODE == 2) {
-            pts[NS - 1][r][0] = XT(o[h].rx); pts[NS - 1][r][1] = XT(o[h].ry); pts[NS - 1][r][2] = XT(o[h].rz);
-          }
-        }
-#pragma unroll
-        for (int s = 0; s < NS; ++s) km[s][r] = __ballot((keep >> s) & 1u);
-      }
-  }
-}
-
-template <int G, int ROW_MODE, int RAYS, typename XT, int NS, int kIt, int NP = 0, int NC = 3>
-__device__ inline void tri_rounds(const MainParams& p, int i, int n_items, const uint2* s_item,
-                                  XT (&pts)[NS][kIt][NC], uint64_t (&km)[NS][kIt]) {
-  tri_rounds_at<G, ROW_MODE, RAYS, XT, NS, kIt, NP, NC>(p, i, n_items, s_item, pts, km);
-}
-
-// Phase B of main3 for rounds [I0, I0 + R), both compile-time (a tile of R <= SLG_TRI_STATIC
-// rounds: I0 = 0; a longer one: rounds 0..3, then the rest), FAST path: ONE gather round trip.
-// tri_rounds_at's groups are serial -- the next group's gathers leave only after the previous
-// combine -- so a tile of 5 or 6 rounds (86 % of the C2 views' tiles) paid two loaded L2 round
-// trips, the second for one or two rounds.  Here every round index is a compile-time constant
-// (the caller dispatches on the block-uniform round count), so there are no r == i + h select
-// chains, and the schedule is:
-//   1. the R codes from LDS (one address, immediate round offsets), then item by item its
-//      column plane's and its row plane's gathers, the code dead once they are out (8 VGPRs a
-//      plane: at most 96 VGPRs of planes in flight at R = 6, when phase A's frame registers
-//      are dead);
-//   2. the items consumed in issue order, singly while SLG_TRI_WIDE or more other items'
-//      planes are held, then SLG_TRI_ILP at a time: each item's pixel is read from LDS one
-//      item ahead and its ray computed just before its combine, so at most SLG_TRI_ILP rays
-//      are live while the later planes land (the compiler's vmcnt waits count down with the
-//      issue order), and every consumed item frees 16 VGPRs of planes for 3 (f32), 6 (f64)
-//      or 2 (keep-t) of point.
-// The scheduling barriers keep the max-ilp scheduler from hoisting the later rays over the
-// earlier combines (which would hold R rays beside R planes).  Per item the fp64 operations,
-// their order, the ballots and the ranks are tri_rounds_at's: the same bits.
-// Register budget (4 waves per SIMD: 128 VGPRs): the f32 two-axis instances sit at 128 and the
-// f64 keep-t ones at 126, none with scratch.  What had to go to get there: the six rounds' (u, v)
-// and in-range flags held from the start (re-read / recomputed per item), one LDS address per
-// round (item_slot is linear in the round), and an out-of-line call (forced inline: MainParams
-// lived in scratch otherwise).  A plane spilled while the gathers are issued costs a vmcnt wait
-// between them, i.e. the second round trip back.  The profiling instance, which carries the
-// phase stamps too, did not fit (32 bytes of scratch, and slower as a whole for it): it defers
-// the last two items' row gathers (LATE) and has none.
-#ifndef SLG_TRI_STATIC
-#define SLG_TRI_STATIC 6                   // tiles of up to this many rounds take tri_rounds_static (0: none)
-#endif
-#ifndef SLG_TRI_ILP
-#define SLG_TRI_ILP 2                      // items whose ray + combine chains are interleaved
-#endif
-#ifndef SLG_TRI_WIDE
-#define SLG_TRI_WIDE 4                     // ... once fewer than this many other items' planes are held
-#endif
-template <int I0, int R, int ROW_MODE, int RAYS, typename XT, int NS, int kIt, int NP = 0, int NC = 3, int LATE = 0>
-__device__ __forceinline__ void tri_rounds_static(const MainParams& p, int n_items, const uint2* s_item,
-                                         XT (&pts)[NS][kIt][NC], uint64_t (&km)[NS][kIt]) {
-  static_assert(I0 >= 0 && R >= 1 && I0 + R <= kIt, "rounds of one tile");
-  const int tid = threadIdx.x;
-  TriPlanes pl[R];
-  uint32_t codes[R];
-  // LATE (the profiling instance, whose phase stamps take the registers): the last LATE items'
-  // row planes, needed last of all, are gathered once item 0 has freed its planes
-  constexpr int kLate = R >= 6 ? LATE : 0;
-  // m < kTilePx: items past n_items are read and masked (code 0, pixel (0, 0), kept by no stream)
-  const int m0 = tid + kTileBlock * I0;             // item of round I0 + h: m0 + kTileBlock * h
-  // ... in slot sl0[kRound * h]: one LDS address and immediate offsets, not one address per round
-  static_assert(kTileBlock % (1 << SLG_ITEM_PAD) == 0, "item_slot is linear in the round");
-  constexpr int kRound = kTileBlock + (kTileBlock >> SLG_ITEM_PAD);
-  const uint2* sl0 = s_item + item_slot(m0);
-#pragma unroll
-  for (int h = 0; h < R; ++h) codes[h] = sl0[kRound * h].x;
-#pragma unroll
-  for (int h = 0; h < R; ++h) {                    // an item's code is dead once its gathers are out
-    const uint32_t code = m0 + kTileBlock * h < n_items ? codes[h] : 0u;
-    tri_planes_col<NP>(p, code, pl[h].pc01, pl[h].pc23);
-    if (h < R - kLate) tri_planes_row<ROW_MODE, NP>(p, code, pl[h].pr01, pl[h].pr23);
-    else codes[h] = code;
-  }
-  // the pixel of an item is read from LDS one item ahead of its ray, not held for all R
-  uint32_t uv_next = sl0[0].y;
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int h = 0; h < R; ++h) {
-    {
-      const bool in = m0 + kTileBlock * h < n_items;
-      const uint32_t uv = in ? uv_next : 0u;
-      if (h + 1 < R) uv_next = sl0[kRound * (h + 1)].y;
-      double r0, r1, r2;
-      tri_ray<RAYS, true>(p, int(uv & 0xffffu), int(uv >> 16), r0, r1, r2);
-      const TriOut o = tri_combine<ROW_MODE, true, NP>(p, pl[h], r0, r1, r2);
-      const uint32_t keep = in ? o.keep : 0u;
-      if constexpr (NC == 1) {                     // the ray parameters only (x64_keep_t)
-        pts[0][I0 + h][0] = o.t;
-        if constexpr (ROW_MODE == 2) pts[NS - 1][I0 + h][0] = o.tr;
-      } else {
-        pts[0][I0 + h][0] = XT(o.x); pts[0][I0 + h][1] = XT(o.y); pts[0][I0 + h][2] = XT(o.z);
-        if constexpr (ROW_MODE == 2) {
-          pts[NS - 1][I0 + h][0] = XT(o.rx); pts[NS - 1][I0 + h][1] = XT(o.ry); pts[NS - 1][I0 + h][2] = XT(o.rz);
-        }
-      }
-#pragma unroll
-      for (int s = 0; s < NS; ++s) km[s][I0 + h] = __ballot((keep >> s) & 1u);
-    }
-    if (kLate > 0 && h == 0) {
-#pragma unroll
-      for (int g = R - kLate; g < R; ++g) tri_planes_row<ROW_MODE, NP>(p, codes[g], pl[g].pr01, pl[g].pr23);
-    }
-    // a group ends here: items go singly while SLG_TRI_WIDE or more others' planes are still
-    // held, then SLG_TRI_ILP at a time (counted from the last item)
-    const int left = R - 1 - h;
-    if (left >= SLG_TRI_WIDE || left % SLG_TRI_ILP == 0) __builtin_amdgcn_sched_barrier(0);
-  }
-}
 
 // PROF: the profiling instance (SLG_DBG set): honours the ablation bits of MainParams::dbg and
 // writes per-workgroup phase records; the production instances carry none of that code.
@@ -1563,7 +322,7 @@ __global__ __launch_bounds__(kTileBlock, ROW_MODE == 2 && XYZ64 ? 2 : SLG_M3_WAV
 #pragma unroll
       for (int g = 0; g + SLG_TRI_GROUP <= kIt; g += SLG_TRI_GROUP)
         if (i + SLG_TRI_GROUP <= rounds) {
-          tri_rounds<SLG_TRI_GROUP, ROW_MODE, RAYS, XT, NS, kIt, NP>(p, g, n_items, s_item, pts, km);
+          tri_rounds_at<SLG_TRI_GROUP, ROW_MODE, RAYS, XT, NS, kIt, NP>(p, g, n_items, s_item, pts, km);
           i = g + SLG_TRI_GROUP;
         }
       if (SLG_TRI_GROUP > 2 && i + 2 <= rounds) {
@@ -1604,26 +363,14 @@ __global__ __launch_bounds__(kTileBlock, ROW_MODE == 2 && XYZ64 ? 2 : SLG_M3_WAV
         const uint32_t sc = it.x, suv = it.y;
         const uint32_t code = in ? sc : 0u, uv = in ? suv : 0u;   // ... garbage past n_items masked
         const int u = int(uv & 0xffffu), v = int(uv >> 16);
-        uint32_t keep;
-        if (trivial) {
-          keep = in ? (ROW_MODE == 2 ? 3u : 1u) : 0u;
-          if constexpr (NC == 3) {
-            pts[0][i][0] = XT(code & 0xffff); pts[0][i][1] = XT(code >> 16); pts[0][i][2] = XT(u);
-            if constexpr (ROW_MODE == 2) { pts[NS - 1][i][0] = XT(v); pts[NS - 1][i][1] = 0; pts[NS - 1][i][2] = 0; }
-          }
+        TriOut o{};
+        if (trivial) {                                 // the item's words as its point, kept by every stream
+          o.x = double(code & 0xffff); o.y = double(code >> 16); o.z = double(u); o.rx = double(v);
+          o.keep = ROW_MODE == 2 ? 3u : 1u;
         } else {
-          const TriOut o = tri_item<ROW_MODE, RAYS>(p, code, u, v);
-          keep = in ? o.keep : 0u;
-          if constexpr (NC == 1) {
-            pts[0][i][0] = o.t;
-            if constexpr (ROW_MODE == 2) pts[NS - 1][i][0] = o.tr;
-          } else {
-            pts[0][i][0] = XT(o.x); pts[0][i][1] = XT(o.y); pts[0][i][2] = XT(o.z);
-            if constexpr (ROW_MODE == 2) { pts[NS - 1][i][0] = XT(o.rx); pts[NS - 1][i][1] = XT(o.ry); pts[NS - 1][i][2] = XT(o.rz); }
-          }
+          o = tri_item<ROW_MODE, RAYS>(p, code, u, v);
         }
-#pragma unroll
-        for (int s = 0; s < NS; ++s) km[s][i] = __ballot((keep >> s) & 1u);
+        tri_store(o, in ? o.keep : 0u, i, pts, km);
       }
       if (lane == 0) {
 #pragma unroll
@@ -1793,25 +540,11 @@ __global__ __launch_bounds__(kBlock) void pinhole_kernel(const double* rays, int
 
 // ------------------------------------------------------------------ host side
 thread_local char g_err[512] = "";         // slg_last_error(); written by slg_internal_fail alone
-const auto fail = slg_internal_fail;       // (this file's short name for it)
 
 int ceil_log2(int n) {
   int b = 0;
   while ((1ll << b) < (long long)n) ++b;
   return b;
-}
-
-int check_enough_frames(const slg_capture* cap) {
-  if (cap->n_frames < 4)
-    return fail(SLG_ERR_NOT_ENOUGH, "Not enough images (got %d, need at least 4).", cap->n_frames);
-  return SLG_OK;
-}
-
-// The slices of a launch lie ws_stride apart: checked once there is a second one.
-int check_ws_stride(bool several, int64_t ws_stride, int64_t n_px) {
-  if (several && (ws_stride < ws_total(n_px) || (ws_stride & 255)))
-    return fail(SLG_ERR_INVALID, "ws_stride too small or not 256-aligned");
-  return SLG_OK;
 }
 
 // Which frames each axis reads and how the code is shifted (processing.py:80-122,
@@ -1850,76 +583,6 @@ int make_plan(const slg_capture* cap, const slg_decode_params* dp, Plan* out) { 
     return fail(SLG_ERR_INVALID, "unknown variant %d", dp->variant);
   }
   return SLG_OK;
-}
-
-int check_capture(const slg_capture* cap) {
-  if (!cap || !cap->frames) return fail(SLG_ERR_INVALID, "capture frames is NULL");
-  if (cap->height < 1 || cap->width < 1) return fail(SLG_ERR_INVALID, "bad image size %dx%d", cap->width, cap->height);
-  const int64_t n_px = int64_t(cap->height) * cap->width;
-  if (n_px >= (int64_t(1) << 31)) return fail(SLG_ERR_UNSUPPORTED, "image larger than 2^31 pixels");
-  if (n_px * 3 + 64 >= (int64_t(1) << 32))        // texture reads take 32-bit byte offsets
-    return fail(SLG_ERR_UNSUPPORTED, "image larger than 1.43e9 pixels");
-  if (cap->height > 65535 || cap->width > 65535) return fail(SLG_ERR_UNSUPPORTED, "image side above 65535 pixels");
-  if (cap->frame_stride < ((n_px + 7) & ~int64_t(7)) || (cap->frame_stride & 7))
-    return fail(SLG_ERR_INVALID, "frame_stride must be >= round_up(H*W, 8) and a multiple of 8");
-  if (reinterpret_cast<uintptr_t>(cap->frames) & 7) return fail(SLG_ERR_INVALID, "frames must be 8-byte aligned");
-  if (int64_t(cap->n_frames > 0 ? cap->n_frames : 0) * cap->frame_stride >= (int64_t(1) << 32))
-    return fail(SLG_ERR_UNSUPPORTED, "frame stack larger than 4 GiB");   // 32-bit buffer offsets
-  return SLG_OK;
-}
-
-int debug_flags();
-
-// One stats launch for n_views views (<= kMaxBatch) of one geometry; view v reads white/black
-// from whites[v] / blacks[v] and owns the workspace slice at workspace + v * ws_stride.
-// from_parts: Otsu from the per-tile partial histograms in each slice (written by a fused
-// launch's next-batch pass) instead of from white/black frames.
-int stats_launch_batch(const uint8_t* const* whites, const uint8_t* const* blacks, int n_views, int64_t n_px,
-                       const slg_decode_params* dp, char* workspace, int64_t ws_stride, hipStream_t s,
-                       bool from_parts = false, uint32_t* hist_out = nullptr) {
-  StatsParams sp{};
-  sp.hist_out = hist_out;
-  for (int v = 0; v < n_views; ++v) {
-    sp.white[v] = whites ? whites[v] : nullptr;
-    sp.black[v] = blacks ? blacks[v] : nullptr;
-    sp.wsv[v] = reinterpret_cast<WsHeader*>(workspace + int64_t(v) * ws_stride);
-    if (from_parts) sp.parts[v] = reinterpret_cast<const uint32_t*>(workspace + int64_t(v) * ws_stride + parts_off(n_px));
-  }
-  sp.n_parts = n_tiles_of(n_px);
-  sp.pad_zero = from_parts ? sp.n_parts * kTilePx - n_px : align_up(n_px, kHistChunk) - n_px;
-  sp.n_px = n_px;
-  sp.n_state_words = n_state_words(n_px);
-  sp.thresh_mode = dp ? dp->thresh_mode : SLG_THRESH_MANUAL;
-  sp.shadow_val = dp ? dp->shadow_val : 0.0;
-  sp.contrast_val = dp ? dp->contrast_val : 0.0;
-  // Few fat workgroups per view: each merges its sub-histograms into the view's histogram with
-  // <= 512 global atomics, and a batch's stats pass takes few CU slots next to a fused launch.
-  // One-view Otsu launches: kOtsuOneChunks MFMA chunks per wave.
-  const bool otsu_one = n_views == 1 && sp.thresh_mode == SLG_THRESH_OTSU;
-  const int64_t px_per_block = otsu_one ? int64_t(kBlock / 64) * kHistChunk * kOtsuOneChunks : int64_t(kBlock) * kStatsPx;
-  int64_t grid = (n_px + px_per_block - 1) / px_per_block;
-  const int64_t cap = otsu_one ? 4 * kStatsBlocksOne : n_views == 1 ? kStatsBlocksOne
-                    : sp.thresh_mode == SLG_THRESH_OTSU ? kStatsBlocksOtsu : kStatsBlocks;
-  if (grid > cap) grid = cap;
-  if (sp.thresh_mode == SLG_THRESH_OTSU) {   // bound chunks per wave (i32 MFMA accumulators)
-    const int64_t per_block = int64_t(kBlock / 64) * kHistChunk * kHistMaxChunks;
-    const int64_t need = (n_px + per_block - 1) / per_block;
-    if (grid < need) grid = need;
-  }
-  if (from_parts) {   // ~2 x kPartsInFlight tiles per workgroup: one or two rounds of loads
-    grid = (sp.n_parts + 2 * kPartsInFlight - 1) / (2 * kPartsInFlight);
-    grid = grid < 1 ? 1 : (grid > kPartsBlocksMax ? kPartsBlocksMax : grid);
-    hipLaunchKernelGGL(parts_kernel, dim3(unsigned(grid), unsigned(n_views)), dim3(kBlock), 0, s, sp);
-    return check_launch("parts_kernel");
-  }
-  if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(stats_kernel, dim3(unsigned(grid), unsigned(n_views)), dim3(kBlock), 0, s, sp);
-  return check_launch("stats_kernel");
-}
-
-int stats_launch(const uint8_t* white, const uint8_t* black, int64_t n_px, const slg_decode_params* dp,
-                 void* workspace, hipStream_t s) {
-  return stats_launch_batch(&white, &black, 1, n_px, dp, static_cast<char*>(workspace), 0, s);
 }
 
 int fill_calib(MainParams& mp, const slg_calib* c, const slg_tri_params* tp, int64_t n_px, int width) {
@@ -2133,8 +796,7 @@ int check_batch(const slg_capture* caps, int n_views) {
     const int rc = check_capture(&caps[v]);
     if (rc) return rc;
     if (reinterpret_cast<uintptr_t>(caps[v].texture) & 7) return fail(SLG_ERR_INVALID, "texture must be 8-byte aligned");
-    if (caps[v].height != caps[0].height || caps[v].width != caps[0].width)
-      return fail(SLG_ERR_INVALID, "all views of a batch must share one geometry");
+    if (const int rg = check_same_geometry(caps[v], caps[0], kBatchGeometry)) return rg;
   }
   return SLG_OK;
 }
@@ -2161,8 +823,7 @@ int fused_batch(const slg_capture* caps, int n_views, const slg_decode_params* d
       rc = check_capture(&next[v]);
       if (!rc) rc = check_enough_frames(&next[v]);
       if (rc) return rc;
-      if (next[v].height != caps[0].height || next[v].width != caps[0].width)
-        return fail(SLG_ERR_INVALID, "next batch must share this batch's geometry");
+      if ((rc = check_same_geometry(next[v], caps[0], "next batch must share this batch's geometry"))) return rc;
     }
   }
   std::vector<Plan> plans(static_cast<size_t>(n_views));   // one make_plan per view: it validates too
@@ -2232,34 +893,6 @@ int fused_batch(const slg_capture* caps, int n_views, const slg_decode_params* d
   return SLG_OK;
 }
 
-// Stats of n_views views (one launch per kMaxBatch views).
-int stats_batch(const slg_capture* caps, int n_views, const slg_decode_params* dp, char* ws, int64_t ws_stride,
-                hipStream_t s) {
-  if (!caps || n_views < 1 || !dp || !ws) return fail(SLG_ERR_INVALID, "NULL argument");
-  if (dp->thresh_mode < 0 || dp->thresh_mode > 2) return fail(SLG_ERR_INVALID, "bad thresh_mode");
-  for (int v = 0; v < n_views; ++v) {
-    int rc = check_capture(&caps[v]);
-    if (!rc) rc = check_enough_frames(&caps[v]);
-    if (rc) return rc;
-    if (caps[v].height != caps[0].height || caps[v].width != caps[0].width)
-      return fail(SLG_ERR_INVALID, "all views of a batch must share one geometry");
-  }
-  const int64_t n_px = int64_t(caps[0].height) * caps[0].width;
-  if (const int rc = check_ws_stride(n_views > 1, ws_stride, n_px)) return rc;
-  for (int v0 = 0; v0 < n_views; v0 += kMaxBatch) {
-    const int nb = n_views - v0 < kMaxBatch ? n_views - v0 : kMaxBatch;
-    const uint8_t* wh[kMaxBatch];
-    const uint8_t* bl[kMaxBatch];
-    for (int v = 0; v < nb; ++v) {
-      wh[v] = caps[v0 + v].frames;
-      bl[v] = caps[v0 + v].frames + caps[v0 + v].frame_stride;
-    }
-    const int rc = stats_launch_batch(wh, bl, nb, n_px, dp, ws + int64_t(v0) * ws_stride, ws_stride, s);
-    if (rc) return rc;
-  }
-  return SLG_OK;
-}
-
 }  // namespace
 
 // The library's one error entry (internal.h).
@@ -2322,49 +955,6 @@ int32_t slg_workspace_init(void* workspace, int64_t workspace_bytes, void* strea
   return SLG_OK;
 }
 
-int32_t slg_decode_stats(const slg_capture* cap, const slg_decode_params* dp, void* workspace, void* stream) {
-  int rc = check_capture(cap);
-  if (rc) return rc;
-  if (!dp || !workspace) return fail(SLG_ERR_INVALID, "NULL argument");
-  if ((rc = check_enough_frames(cap))) return rc;
-  if (dp->thresh_mode < 0 || dp->thresh_mode > 2) return fail(SLG_ERR_INVALID, "bad thresh_mode");
-  const int64_t n_px = int64_t(cap->height) * cap->width;
-  return stats_launch(cap->frames, cap->frames + cap->frame_stride, n_px, dp, workspace,
-                      static_cast<hipStream_t>(stream));
-}
-
-int32_t slg_decode_histograms(const slg_capture* cap, const slg_decode_params* dp, void* workspace,
-                              uint32_t* hist_out, void* stream) {
-  int rc = check_capture(cap);
-  if (rc) return rc;
-  if (!dp || !workspace || !hist_out) return fail(SLG_ERR_INVALID, "NULL argument");
-  if ((rc = check_enough_frames(cap))) return rc;
-  if (dp->thresh_mode != SLG_THRESH_OTSU && dp->thresh_mode != SLG_THRESH_PERCENTILE)
-    return fail(SLG_ERR_INVALID, "histograms serve Otsu / percentile thresholds (manual ones need none)");
-  if (reinterpret_cast<uintptr_t>(hist_out) & 3) return fail(SLG_ERR_INVALID, "hist_out must be 4-byte aligned");
-  const int64_t n_px = int64_t(cap->height) * cap->width;
-  const uint8_t* white = cap->frames;
-  const uint8_t* black = cap->frames + cap->frame_stride;
-  return stats_launch_batch(&white, &black, 1, n_px, dp, static_cast<char*>(workspace), 0,
-                            static_cast<hipStream_t>(stream), false, hist_out);
-}
-
-int32_t slg_thresholds_from_histograms(const uint32_t* hist, int64_t n_pixels, const slg_decode_params* dp,
-                                       void* workspace, int64_t n_band_pixels, void* stream) {
-  if (!hist || !dp || !workspace) return fail(SLG_ERR_INVALID, "NULL argument");
-  if (n_pixels < 1 || n_band_pixels < 1 || n_band_pixels > n_pixels || n_pixels >= (int64_t(1) << 31))
-    return fail(SLG_ERR_INVALID, "need 1 <= n_band_pixels <= n_pixels < 2^31");
-  if (dp->thresh_mode != SLG_THRESH_OTSU && dp->thresh_mode != SLG_THRESH_PERCENTILE)
-    return fail(SLG_ERR_INVALID, "histograms serve Otsu / percentile thresholds (manual ones need none)");
-  if (reinterpret_cast<uintptr_t>(hist) & 3) return fail(SLG_ERR_INVALID, "hist must be 4-byte aligned");
-  const int64_t nsw = n_state_words(n_band_pixels);
-  int64_t grid = (nsw + kBlock - 1) / kBlock;
-  grid = grid < 1 ? 1 : (grid > 64 ? 64 : grid);
-  hipLaunchKernelGGL(hist_thresholds_kernel, dim3(unsigned(grid)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
-                     hist, reinterpret_cast<WsHeader*>(workspace), n_pixels, dp->thresh_mode, nsw);
-  return check_launch("hist_thresholds_kernel");
-}
-
 int32_t slg_decode(const slg_capture* cap, const slg_decode_params* dp, void* workspace, int32_t* col_out,
                    int32_t* row_out, uint8_t* mask_out, void* stream) {
   int rc = check_capture(cap);
@@ -2406,7 +996,7 @@ int32_t slg_triangulate(const slg_maps* maps, const slg_calib* calib, const slg_
   m3.c.n_tiles = n_tiles_of(n_px);
   m3.n_views = 1;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  rc = stats_launch(nullptr, nullptr, n_px, nullptr, workspace, s);   // arms states only (manual mode)
+  rc = slg_stats_arm(n_px, workspace, s);
   if (rc) return rc;
   m3.v[0].in_col = maps->col; m3.v[0].in_row = maps->row; m3.v[0].in_mask = maps->mask;
   m3.v[0].texture = maps->texture;
@@ -2423,7 +1013,7 @@ static int reconstruct_impl(const slg_capture* cap, const slg_decode_params* dp,
   if (with_stats) {
     int rc = check_batch(cap, 1);
     if (!rc) rc = make_plan(cap, dp, nullptr);
-    if (!rc) rc = stats_batch(cap, 1, dp, static_cast<char*>(workspace), 0, s);
+    if (!rc) rc = slg_stats_batch(cap, 1, dp, static_cast<char*>(workspace), 0, s);
     if (rc) return rc;
   }
   return fused_batch(cap, 1, dp, calib, tp, static_cast<char*>(workspace), 0, out, nullptr, s);
@@ -2451,18 +1041,13 @@ int32_t slg_reconstruct_batch(const slg_capture* caps, int32_t n_views, const sl
   if (rc) return rc;
   for (int v0 = 0, launch = 0; v0 < n_views; v0 += kMaxViews, ++launch) {
     const int nb = n_views - v0 < kMaxViews ? n_views - v0 : kMaxViews;
-    rc = stats_batch(caps + v0, nb, dp, ws + int64_t(v0) * ws_stride, ws_stride, s);
+    rc = slg_stats_batch(caps + v0, nb, dp, ws + int64_t(v0) * ws_stride, ws_stride, s);
     if (rc) return rc;
     rc = fused_batch(caps + v0, nb, dp, calib, tp, ws + int64_t(v0) * ws_stride, ws_stride, outs + v0,
                      timing_events ? timing_events + 2 * launch : nullptr, s);
     if (rc) return rc;
   }
   return SLG_OK;
-}
-
-int32_t slg_decode_stats_batch(const slg_capture* caps, int32_t n_views, const slg_decode_params* dp,
-                               void* workspace, int64_t ws_stride, void* stream) {
-  return stats_batch(caps, n_views, dp, static_cast<char*>(workspace), ws_stride, static_cast<hipStream_t>(stream));
 }
 
 int32_t slg_decode_triangulate_batch(const slg_capture* caps, int32_t n_views, const slg_decode_params* dp,
@@ -2489,22 +1074,6 @@ int32_t slg_decode_triangulate_batch_carry(const slg_capture* caps, int32_t n_vi
   return fused_batch(caps, n_views, dp, calib, tp, static_cast<char*>(workspace), ws_stride, outs, timing_events,
                      static_cast<hipStream_t>(stream), next, next ? n_next : 0, static_cast<char*>(fin_workspace),
                      fin_workspace ? n_fin : 0);
-}
-
-int32_t slg_decode_stats_partials_batch(int32_t n_views, int32_t height, int32_t width, const slg_decode_params* dp,
-                                        void* workspace, int64_t ws_stride, void* stream) {
-  if (n_views < 1 || !dp || !workspace || height < 1 || width < 1) return fail(SLG_ERR_INVALID, "bad argument");
-  if (dp->thresh_mode != SLG_THRESH_OTSU) return fail(SLG_ERR_UNSUPPORTED, "partial histograms are Otsu only");
-  const int64_t n_px = int64_t(height) * width;
-  if (const int rc = check_ws_stride(n_views > 1, ws_stride, n_px)) return rc;
-  char* ws = static_cast<char*>(workspace);
-  for (int v0 = 0; v0 < n_views; v0 += kMaxBatch) {
-    const int nb = n_views - v0 < kMaxBatch ? n_views - v0 : kMaxBatch;
-    const int rc = stats_launch_batch(nullptr, nullptr, nb, n_px, dp, ws + int64_t(v0) * ws_stride, ws_stride,
-                                      static_cast<hipStream_t>(stream), true);
-    if (rc) return rc;
-  }
-  return SLG_OK;
 }
 
 int32_t slg_workspace_set_arena(void* workspace, int64_t ws_stride, int32_t n_slices, int64_t* cursor,

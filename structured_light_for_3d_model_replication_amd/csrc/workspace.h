@@ -50,9 +50,14 @@ constexpr int kHistCopies = 16;            // partial histograms: blocks spread 
 constexpr int64_t kHistPartOff = 8192;      // uint32 [kHistCopies][2][256] after the header
 constexpr int64_t kHeaderBytes = 65536;
 static_assert(sizeof(WsHeader) <= kHistPartOff, "header");
-static_assert(offsetof(WsHeader, error) == 3084 && offsetof(WsHeader, totals) == 3120 && offsetof(WsHeader, above) == 3136 &&
-              offsetof(WsHeader, arena_off) == 3152,
-              "header offsets the host reads (engine.py: error word, WS_TOTALS_OFF, WS_ABOVE_OFF)");
+#define SLG_WS_AT(f, o) (offsetof(WsHeader, f) == (o))
+static_assert(SLG_WS_AT(hist, 0) && SLG_WS_AT(max_diff_enc, 3072) && SLG_WS_AT(ticket, 3076) && SLG_WS_AT(lb_ticket, 3080) &&
+              SLG_WS_AT(error, 3084) && SLG_WS_AT(smin, 3088) && SLG_WS_AT(cmin, 3092) && SLG_WS_AT(lb_ticket_row, 3096) &&
+              SLG_WS_AT(pad0, 3100) && SLG_WS_AT(thr_s, 3104) && SLG_WS_AT(thr_c, 3112) && SLG_WS_AT(totals, 3120) &&
+              SLG_WS_AT(above, 3136) && SLG_WS_AT(arena_off, 3152) && SLG_WS_AT(arena_mult, 3160) && SLG_WS_AT(pad4, 3164) &&
+              SLG_WS_AT(arena_cursor, 3168) && SLG_WS_AT(arena_cap, 3176) && SLG_WS_AT(pad3, 3184) && sizeof(WsHeader) == 3200,
+              "the header the host reads: engine.py's WS_HEADER dtype names every field (tests/test_ws_header.py)");
+#undef SLG_WS_AT
 
 __host__ __device__ inline int64_t n_tiles_of(int64_t n_px) { return (n_px + kTilePx - 1) / kTilePx; }
 __host__ __device__ inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }

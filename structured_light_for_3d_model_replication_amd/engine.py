@@ -351,10 +351,14 @@ class Reconstructor:
         N.check(N.lib().slg_thresholds_from_histograms(_vp(hist), int(n_px_view), ctypes.byref(dp),
                                                        _vp(self.workspace), self.n_px, _stream(stream)))
 
+    def _header(self) -> np.void:
+        """The workspace header as one ``WS_HEADER`` record.  One host sync."""
+        return self.workspace[:WS_HEADER.itemsize].cpu().numpy().view(WS_HEADER)[0]
+
     def column_points(self) -> int:
         """Column-cloud points of the last row_mode-2 launch (``WsHeader.totals[0]``; its cloud is
         the column cloud, then the row cloud).  One host sync."""
-        return int(self.workspace[WS_TOTALS_OFF: WS_TOTALS_OFF + 8].cpu().view(torch.int64).item())
+        return int(self._header()["totals"][0])
 
     def decode_triangulate(self, frames: DeviceFrames, cfg: DecodeConfig, calib: DeviceCalib,
                            out: "Cloud", row_mode=1, epipolar_tol=2.0, stream=None,
@@ -375,18 +379,24 @@ class Reconstructor:
 
     def thresholds(self):
         """(shadow, contrast) float thresholds of the last stats pass (workspace header)."""
-        hdr = self.workspace[:8192].cpu().numpy()
-        off = 3 * 256 * 4 + 4 * 4 + 4 * 4
-        return tuple(np.frombuffer(hdr[off: off + 16].tobytes(), dtype=np.float64))
+        h = self._header()
+        return (h["thr_s"], h["thr_c"])
 
     def error_flags(self) -> int:
-        hdr = self.workspace[:8192].cpu().numpy()
-        return int(np.frombuffer(hdr[3 * 256 * 4 + 12: 3 * 256 * 4 + 16].tobytes(), np.uint32)[0])
+        return int(self._header()["error"])
 
 
-MAX_VIEWS_PER_LAUNCH = 16     # kMaxViews in csrc/slgpu.hip
-WS_ABOVE_OFF = 3136           # offsetof(WsHeader, above) in csrc/workspace.h (static_assert there)
-WS_TOTALS_OFF = 3120          # offsetof(WsHeader, totals)
+MAX_VIEWS_PER_LAUNCH = 16     # kMaxViews in csrc/fused_params.h
+# WsHeader of csrc/workspace.h, field for field (a static_assert there and tests/test_ws_header.py
+# hold the two together); the header's room in a workspace slice is WS_HEADER_BYTES (kHistPartOff).
+WS_HEADER = np.dtype([
+    ("hist", "<u4", (3, 256)), ("max_diff_enc", "<u4"), ("ticket", "<u4"), ("lb_ticket", "<u4"), ("error", "<u4"),
+    ("smin", "<i4"), ("cmin", "<i4"), ("lb_ticket_row", "<u4"), ("pad0", "<i4"), ("thr_s", "<f8"), ("thr_c", "<f8"),
+    ("totals", "<i8", (2,)), ("above", "<i8", (2,)), ("arena_off", "<i8"), ("arena_mult", "<i4"), ("pad4", "<i4"),
+    ("arena_cursor", "<u8"), ("arena_cap", "<i8"), ("pad3", "<u8", (2,))], align=True)
+WS_HEADER_BYTES = 8192
+WS_ABOVE_OFF = WS_HEADER.fields["above"][1]
+WS_TOTALS_OFF = WS_HEADER.fields["totals"][1]
 
 
 @dataclass
@@ -447,7 +457,7 @@ class BatchReconstructor:
     def header(self, slot: int, view: int) -> torch.Tensor:
         """Workspace header (thresholds, flags) of one view slice."""
         off = (slot * self.max_views + view) * self.ws_stride
-        return self.workspace[off: off + 8192]
+        return self.workspace[off: off + WS_HEADER_BYTES]
 
     def prepare(self, frames, cfg: DecodeConfig, calib: DeviceCalib, outs, row_mode=1, epipolar_tol=2.0,
                 slot: int = 0) -> PreparedBatch:
