@@ -847,6 +847,71 @@ int32_t slg_mesh_triangle_normals(const double *vertices, const int32_t *triangl
 int32_t slg_mesh_stl_pack(const double *vertices, const int32_t *triangles, const double *normals,
                           int64_t n_triangles, uint8_t *records_out, void *stream);
 
+/* ---- Mesh post-processing (csrc/cloud_meshpost.hip): what the device takes of the
+ * reference's MeshLab step (server/processing.py:742-787): vertex adjacency, Laplacian and Taubin
+ * smoothing, the closing of small holes.  Our rules, MeshLab / VCGlib parity unpinned; the same
+ * input gives the same bits.  Asynchronous on `stream`.  triangles int32 [T][3] with indices in
+ * 0..V-1 (any other sets SLG_FILTER_BAD_INDEX in the status word; later kernels then return).
+ *
+ * The workspaces, slg_mesh_post_ws_bytes(stage, V, T) bytes and 256-byte aligned, begin with the
+ * mesh header: int32 status at byte 0, int64 nV at 8, int64 nT at 16, and int64 stats[8] at 128.
+ * The stage numbers continue those of slg_mesh_ws_bytes.  A directed pair is the key src << 32 | dst.
+ *
+ *   slg_mesh_adjacency_count  the six directed pairs of every triangle, sorted, unique, no
+ *                        self-pair: header nV = entries of the adjacency CSR.  The winding pairs
+ *                        a->b, b->c, c->a alone: (a, b) is a boundary edge iff (b, a) is not
+ *                        among them; header nT = entries of the boundary CSR (both directions of
+ *                        every boundary edge, unique).
+ *   slg_mesh_adjacency_emit   (same workspace, untouched in between) offsets int64 [V+1] and
+ *                        neighbours int32 ascending per row; boundary uint8 [V] (1: an endpoint
+ *                        of a boundary edge) and the boundary CSR likewise.
+ *   slg_mesh_smooth_pass one Jacobi pass out = f(in), out != in.  N(v) is the boundary row of a
+ *                        boundary vertex, the adjacency row otherwise; s = ((q0 + q1) + q2) + ..
+ *                        per component in row order, c = |N(v)|; c == 0 copies p.
+ *                        SLG_MESH_SMOOTH_LAPLACIAN: p' = (p + s) / (c + 1).  SLG_MESH_SMOOTH_STEP:
+ *                        m = s / c, p' = p + (m - p) * factor (Taubin: factor lam, then mu).
+ *   slg_mesh_holes_count B = the boundary edges in ascending key order; next(a, b) = the first
+ *                        edge of B with source b.  A vertex is blocked when its in or out degree
+ *                        along B is not 1 while it has any, or when a winding pair through it
+ *                        occurs twice.  Every edge walks next for at most max_size (3..64) steps:
+ *                        closable when back at itself after 3 <= L <= max_size steps without
+ *                        touching a blocked vertex; the loop's leader is its smallest index in B.
+ *                        Header nT = new triangles (L - 2 per loop), stats[SLG_MESH_HOLES_STAT_*].
+ *   slg_mesh_holes_emit  (same workspace) the new triangles in ascending (leader, clip step) into
+ *                        triangles_out [nT][3]: ring r[0..m-1] from the leader's source in walk
+ *                        order; while m > 3 the i with the smallest squared diagonal
+ *                        (dx dx + dy dy) + dz dz between r[i-1] and r[i+1] (ties: lowest i) gives
+ *                        (r[i+1], r[i], r[i-1]) and leaves; last (r[2], r[1], r[0]).  No
+ *                        self-intersection or existing-edge check.
+ *
+ * SLG_ERR_INVALID for a NULL or misaligned buffer, V or T <= 0, V >= 2^31, 3 T > 2^30, max_size
+ * outside 3..64, an unknown stage or mode, or a workspace that is too small. */
+#define SLG_MESH_WS_ADJACENCY 8
+#define SLG_MESH_WS_HOLES 9
+#define SLG_MESH_SMOOTH_LAPLACIAN 0
+#define SLG_MESH_SMOOTH_STEP 1
+#define SLG_MESH_HOLES_MAX_SIZE 64
+#define SLG_MESH_HOLES_STAT_EDGES 0          /* boundary edges */
+#define SLG_MESH_HOLES_STAT_LOOPS 1          /* closable loops */
+#define SLG_MESH_HOLES_STAT_CLOSABLE_EDGES 2 /* edges on closable loops */
+#define SLG_MESH_HOLES_STAT_LONG_EDGES 3     /* edges whose walk ran max_size steps: loops left open by size */
+#define SLG_MESH_HOLES_STAT_BLOCKED_EDGES 4  /* edges whose walk touched a blocked vertex */
+int64_t slg_mesh_post_ws_bytes(int32_t stage, int64_t n_vertices, int64_t n_triangles);
+int32_t slg_mesh_adjacency_count(const int32_t *triangles, int64_t n_triangles, int64_t n_vertices, void *ws,
+                                 int64_t ws_bytes, void *stream);
+int32_t slg_mesh_adjacency_emit(int64_t n_triangles, int64_t n_vertices, void *ws, int64_t ws_bytes,
+                                int64_t *offsets_out, int32_t *neighbours_out, int64_t n_neighbours,
+                                uint8_t *boundary_out, int64_t *boundary_offsets_out,
+                                int32_t *boundary_neighbours_out, int64_t n_boundary_neighbours, void *stream);
+int32_t slg_mesh_smooth_pass(const double *vertices, double *vertices_out, int64_t n_vertices,
+                             const int64_t *offsets, const int32_t *neighbours, const uint8_t *boundary,
+                             const int64_t *boundary_offsets, const int32_t *boundary_neighbours, int32_t mode,
+                             double factor, void *stream);
+int32_t slg_mesh_holes_count(const int32_t *triangles, int64_t n_triangles, int64_t n_vertices, int32_t max_size,
+                             void *ws, int64_t ws_bytes, void *stream);
+int32_t slg_mesh_holes_emit(const double *vertices, int64_t n_vertices, int64_t n_triangles, void *ws,
+                            int64_t ws_bytes, int32_t *triangles_out, int64_t n_new_triangles, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,11 +187,23 @@ EXPORTS = {
     "slg_mesh_remove": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "slg_mesh_triangle_normals": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     "slg_mesh_stl_pack": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "slg_mesh_post_ws_bytes": (c_i64, [c_i32, c_i64, c_i64]),
+    "slg_mesh_adjacency_count": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp]),
+    "slg_mesh_adjacency_emit": (c_i32, [c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "slg_mesh_smooth_pass": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_dbl, c_vp]),
+    "slg_mesh_holes_count": (c_i32, [c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp]),
+    "slg_mesh_holes_emit": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
 }
 MESH_HDR_BYTES, MESH_MAX_DEPTH = 256, 10         # SLG_MESH_HDR_BYTES; kMaxDepth of csrc/cloud_mesh.hip
 # SLG_MESH_WS_*: the stages of slg_mesh_ws_bytes
 (MESH_WS_GRID, MESH_WS_SPLAT, MESH_WS_SOLVE, MESH_WS_ISO, MESH_WS_EXTRACT, MESH_WS_QUANTILE, MESH_WS_REMOVE,
  MESH_WS_ALL) = range(8)
+MESH_WS_ADJACENCY, MESH_WS_HOLES = 8, 9          # the stages of slg_mesh_post_ws_bytes (csrc/cloud_meshpost.hip)
+MESH_SMOOTH_LAPLACIAN, MESH_SMOOTH_STEP = 0, 1   # SLG_MESH_SMOOTH_*
+MESH_HOLES_MAX_SIZE = 64                         # SLG_MESH_HOLES_MAX_SIZE
+# SLG_MESH_HOLES_STAT_*: indices into the header's stats after slg_mesh_holes_count
+(MESH_HOLES_STAT_EDGES, MESH_HOLES_STAT_LOOPS, MESH_HOLES_STAT_CLOSABLE_EDGES, MESH_HOLES_STAT_LONG_EDGES,
+ MESH_HOLES_STAT_BLOCKED_EDGES) = range(5)
 ORIENT_MAX_K, ORIENT_STATS_LEN = 128, 128        # SLG_ORIENT_MAX_K, SLG_ORIENT_STATS_LEN
 # SLG_ORIENT_STAT_*: indices into the stats of slg_emst / slg_orient_tangent
 (ORIENT_STAT_EMST_ROUNDS, ORIENT_STAT_TREE_ROUNDS, ORIENT_STAT_LIST_FAR, ORIENT_STAT_WALKED, ORIENT_STAT_FAR,

@@ -31,7 +31,8 @@ CSRC = os.path.join(PKG, "csrc")
 SRCS = [os.path.join(CSRC, n) for n in ("slgpu.hip", "stats.hip", "ply.hip", "color_gray.hip", "png_device.hip",
                                         "cloud_grid.hip", "cloud_filter.hip", "cloud_cluster.hip",
                                         "cloud_normals.hip", "cloud_icp.hip", "cloud_feature.hip",
-                                        "cloud_ransac.hip", "cloud_plane.hip", "cloud_orient.hip", "cloud_mesh.hip", "code_object.cpp",
+                                        "cloud_ransac.hip", "cloud_plane.hip", "cloud_orient.hip", "cloud_mesh.hip", "cloud_meshpost.hip",
+                                        "code_object.cpp",
                                         "png_gray.cpp",
                                         "gather.cpp")]
 SRC_SUFFIXES = (".hip", ".cpp", ".h")

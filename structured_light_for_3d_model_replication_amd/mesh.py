@@ -9,6 +9,11 @@ of the solution at the points as iso value, and marching tetrahedra over Kuhn's 
 cell.  Every step is a pure function of its input; ``tests/mesh_ref.py`` restates each in NumPy and
 the device equals it bit for bit.  Node fields are float64 ``[R+1, R+1, R+1]`` tensors indexed
 ``[z, y, x]``.
+
+Behind it, what the device takes of the reference's MeshLab step (``csrc/cloud_meshpost.hip``,
+DESIGN.md §17): :func:`vertex_adjacency`, :func:`smooth_laplacian`, :func:`smooth_taubin`,
+:func:`close_holes`, :func:`boundary_loops` and :func:`postprocess`, restated in
+``tests/meshpost_ref.py``; parity with MeshLab / VCGlib is unpinned.
 """
 from __future__ import annotations
 
@@ -339,3 +344,239 @@ def read_stl(path):
         raise ValueError(f"{path}: {len(data)} bytes, the header promises {84 + 50 * nt}")
     rec = np.frombuffer(data, dtype=np.dtype([("f", "<f4", 12), ("a", "<u2")]), offset=84, count=nt)
     return rec["f"][:, :3].copy(), rec["f"][:, 3:].reshape(nt, 3, 3).copy()
+
+
+# ----------------------------------------------------------------------------- post-processing
+# What the device takes of the reference's MeshLab step (server/processing.py:742-787): vertex
+# adjacency, Laplacian / Taubin smoothing and hole closing (csrc/cloud_meshpost.hip).  Our rules,
+# restated in tests/meshpost_ref.py and equal to it bit for bit; parity with MeshLab / VCGlib is
+# unpinned.  Quadric edge-collapse decimation stays in the reference.
+_POST_HDR = np.dtype([("status", "<i4"), ("R", "<i4"), ("nV", "<i8"), ("nT", "<i8"), ("unused", "<f8", 13),
+                      ("stats", "<i8", 8)])
+MIN_HOLE_SIZE, MAX_HOLE_SIZE = 3, N.MESH_HOLES_MAX_SIZE
+TAUBIN_LAMBDA, TAUBIN_MU = 0.5, -0.53
+
+
+class MeshAdjacency:
+    """The connectivity of a mesh in HBM: ``offsets`` int64 ``[V+1]`` and ``neighbours`` int32 (the
+    unique neighbours of every vertex, ascending), ``boundary`` uint8 ``[V]`` (1: an endpoint of a
+    boundary edge) and the boundary CSR ``boundary_offsets`` / ``boundary_neighbours`` (a boundary
+    vertex's neighbours along boundary edges in either direction, ascending)."""
+
+    def __init__(self, offsets, neighbours, boundary, boundary_offsets, boundary_neighbours):
+        self.offsets, self.neighbours, self.boundary = offsets, neighbours, boundary
+        self.boundary_offsets, self.boundary_neighbours = boundary_offsets, boundary_neighbours
+
+
+def _post_mesh(mesh, what: str):
+    v, t = mesh.vertices, mesh.triangles
+    if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.float64 and v.ndim == 2 and v.shape[1] == 3):
+        raise ValueError(f"{what}: vertices must be a device float64 [V, 3] tensor")
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.ndim == 2 and t.shape[1] == 3):
+        raise ValueError(f"{what}: triangles must be a device int32 [T, 3] tensor")
+    if len(v) >= 1 << 31 or 3 * len(t) > 1 << 30:
+        raise ValueError(f"{what}: 2^31 vertices or more, or more than 2^30 directed triangle edges")
+    return v.contiguous(), t.contiguous()
+
+
+def _post_ws(stage: int, device, nv: int, nt: int) -> torch.Tensor:
+    need = int(N.lib().slg_mesh_post_ws_bytes(stage, nv, nt))
+    if need < 0:
+        CL._raise(-need)
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def _post_header(ws, what: str):
+    hdr = np.frombuffer(ws[:_POST_HDR.itemsize].cpu().numpy().tobytes(), dtype=_POST_HDR)[0]
+    if int(hdr["status"]) & N.FILTER_BAD_INDEX:
+        raise IndexError(f"{what}: a triangle index lies outside 0 .. V - 1")
+    return hdr
+
+
+def vertex_adjacency(mesh: TriangleMesh, stream=None) -> MeshAdjacency:
+    """The :class:`MeshAdjacency` of ``mesh``.  The six directed pairs of every triangle as 64-bit
+    keys ``src << 32 | dst``: radix sort, unique, scan.  An unreferenced vertex has an empty row, a
+    degenerate triangle gives no self-pair.  A triangle's edge ``(a, b)`` in winding order is a
+    boundary edge iff ``(b, a)`` is no triangle's edge in winding order.  Our rule (DESIGN.md §17);
+    ``IndexError`` for a triangle index outside ``0 .. V - 1``."""
+    vert, tris = _post_mesh(mesh, "vertex_adjacency")
+    nv, nt, dev = len(vert), len(tris), vert.device
+    i64 = dict(dtype=torch.int64, device=dev)
+    if nv == 0 or nt == 0:
+        return MeshAdjacency(torch.zeros(nv + 1, **i64), torch.empty(0, dtype=torch.int32, device=dev),
+                             torch.zeros(nv, dtype=torch.uint8, device=dev), torch.zeros(nv + 1, **i64),
+                             torch.empty(0, dtype=torch.int32, device=dev))
+    lib, st = N.lib(), E._stream(stream)
+    with torch.cuda.device(dev):
+        ws = _post_ws(N.MESH_WS_ADJACENCY, dev, nv, nt)
+        CL._raise(lib.slg_mesh_adjacency_count(E._vp(tris), nt, nv, E._vp(ws), ws.numel(), st))
+        hdr = _post_header(ws, "vertex_adjacency")
+        ne, nb = int(hdr["nV"]), int(hdr["nT"])
+        adj = MeshAdjacency(torch.empty(nv + 1, **i64), torch.empty(ne, dtype=torch.int32, device=dev),
+                            torch.empty(nv, dtype=torch.uint8, device=dev), torch.empty(nv + 1, **i64),
+                            torch.empty(nb, dtype=torch.int32, device=dev))
+        CL._raise(lib.slg_mesh_adjacency_emit(nt, nv, E._vp(ws), ws.numel(), E._vp(adj.offsets), E._vp(adj.neighbours), ne,
+                                              E._vp(adj.boundary), E._vp(adj.boundary_offsets),
+                                              E._vp(adj.boundary_neighbours), nb, st))
+    return adj
+
+
+def _check_iterations(iterations, what: str) -> int:
+    if isinstance(iterations, float) and not iterations.is_integer():
+        raise ValueError(f"{what}: iterations must be a whole number, not {iterations}")
+    iterations = int(iterations)
+    if iterations < 0:
+        raise ValueError(f"{what}: iterations must be >= 0, not {iterations}")
+    return iterations
+
+
+def _check_adjacency(adj, vert, what: str):
+    """A caller's :class:`MeshAdjacency` must be this mesh's: the kernel gathers by its indices."""
+    nv, dev = len(vert), vert.device
+    parts = (("offsets", adj.offsets, torch.int64, nv + 1), ("boundary_offsets", adj.boundary_offsets, torch.int64, nv + 1),
+             ("boundary", adj.boundary, torch.uint8, nv), ("neighbours", adj.neighbours, torch.int32, None),
+             ("boundary_neighbours", adj.boundary_neighbours, torch.int32, None))
+    for name, t, dtype, count in parts:
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and t.ndim == 1 and t.is_contiguous()
+                and (count is None or t.numel() == count)):
+            raise ValueError(f"{what}: adjacency.{name} must be a contiguous {dtype} vector on {dev}"
+                             + (f" of {count} entries (the mesh has {nv} vertices)" if count is not None else ""))
+    ends = torch.stack([adj.offsets[0], adj.offsets[-1], adj.boundary_offsets[0], adj.boundary_offsets[-1]]).tolist()
+    if ends != [0, adj.neighbours.numel(), 0, adj.boundary_neighbours.numel()]:
+        raise ValueError(f"{what}: the adjacency's offsets do not span its neighbour lists")
+    for name, t in (("neighbours", adj.neighbours), ("boundary_neighbours", adj.boundary_neighbours)):
+        if t.numel() and not (0 <= int(t.min()) and int(t.max()) < nv):
+            raise ValueError(f"{what}: adjacency.{name} holds an index outside 0 .. {nv - 1}: it belongs to another mesh")
+    return adj
+
+
+def _smooth(mesh, passes, what, adjacency, stream):
+    """``passes``: the (mode, factor) of every Jacobi pass, one launch each over ping-pong buffers."""
+    vert, _ = _post_mesh(mesh, what)
+    cur = vert.clone()
+    if len(vert) and passes:
+        adj = _check_adjacency(adjacency, vert, what) if adjacency is not None else vertex_adjacency(mesh, stream)
+        lib, st = N.lib(), E._stream(stream)
+        with torch.cuda.device(vert.device):
+            nxt = torch.empty_like(cur)
+            for mode, factor in passes:
+                CL._raise(lib.slg_mesh_smooth_pass(E._vp(cur), E._vp(nxt), len(cur), E._vp(adj.offsets), E._vp(adj.neighbours),
+                                                   E._vp(adj.boundary), E._vp(adj.boundary_offsets),
+                                                   E._vp(adj.boundary_neighbours), mode, float(factor), st))
+                cur, nxt = nxt, cur
+    return TriangleMesh(cur, mesh.triangles, mesh.densities)
+
+
+def smooth_laplacian(mesh: TriangleMesh, iterations: int, adjacency: MeshAdjacency | None = None, stream=None) -> TriangleMesh:
+    """``iterations`` Jacobi passes of the umbrella operator: ``p' = (p + s) / (c + 1)`` with ``s``
+    the sum over the neighbour set ``N(v)`` in ascending index, ``((q0 + q1) + q2) + ..``, and
+    ``c = |N(v)|``; ``c == 0`` leaves ``p``.  ``N(v)`` is the adjacency row of an interior vertex
+    and the boundary row of a boundary vertex, which so slides along the boundary (VCGlib's rule as
+    we recall it; parity with MeshLab is unpinned).  A new mesh: ``triangles`` and ``densities`` are
+    carried over, ``triangle_normals`` is ``None``.  ``ValueError`` for ``iterations < 0``."""
+    iterations = _check_iterations(iterations, "smooth_laplacian")
+    return _smooth(mesh, [(N.MESH_SMOOTH_LAPLACIAN, 0.0)] * iterations, "smooth_laplacian", adjacency, stream)
+
+
+def smooth_taubin(mesh: TriangleMesh, iterations: int, lam: float = TAUBIN_LAMBDA, mu: float = TAUBIN_MU,
+                  adjacency: MeshAdjacency | None = None, stream=None) -> TriangleMesh:
+    """``iterations`` Taubin iterations, two Jacobi passes each: ``m = s / c``,
+    ``p' = p + (m - p) * lam``, then the same with ``mu`` (MeshLab's default of 10 is 20 passes);
+    ``s``, ``c`` and ``N(v)`` as in :func:`smooth_laplacian`.  Our rule, MeshLab parity unpinned.
+    ``ValueError`` for ``iterations < 0`` or a ``lam`` / ``mu`` that is not finite."""
+    iterations = _check_iterations(iterations, "smooth_taubin")
+    if not (np.isfinite(lam) and np.isfinite(mu)):
+        raise ValueError(f"smooth_taubin: lam and mu must be finite, not {lam}, {mu}")
+    return _smooth(mesh, [(N.MESH_SMOOTH_STEP, lam), (N.MESH_SMOOTH_STEP, mu)] * iterations, "smooth_taubin", adjacency,
+                   stream)
+
+
+def check_hole_size(max_size) -> int:
+    max_size = int(max_size)
+    if not MIN_HOLE_SIZE <= max_size <= MAX_HOLE_SIZE:
+        raise ValueError(f"max_size must be in {MIN_HOLE_SIZE}..{MAX_HOLE_SIZE} on the device (one wavefront per loop), "
+                         f"not {max_size}")
+    return max_size
+
+
+_EMPTY_RECORD = dict(boundary_edges=0, closable_loops=0, closable_edges=0, open_by_size_edges=0, blocked_edges=0,
+                     new_triangles=0)
+
+
+def _holes_count(mesh, max_size, what, stream):
+    max_size = check_hole_size(max_size)
+    vert, tris = _post_mesh(mesh, what)
+    if len(vert) == 0 or len(tris) == 0:
+        return vert, tris, None, dict(_EMPTY_RECORD)
+    with torch.cuda.device(vert.device):
+        ws = _post_ws(N.MESH_WS_HOLES, vert.device, len(vert), len(tris))
+        CL._raise(N.lib().slg_mesh_holes_count(E._vp(tris), len(tris), len(vert), max_size, E._vp(ws), ws.numel(),
+                                               E._stream(stream)))
+        hdr = _post_header(ws, what)
+    s = hdr["stats"]
+    return vert, tris, ws, dict(boundary_edges=int(s[N.MESH_HOLES_STAT_EDGES]), closable_loops=int(s[N.MESH_HOLES_STAT_LOOPS]),
+                                closable_edges=int(s[N.MESH_HOLES_STAT_CLOSABLE_EDGES]),
+                                open_by_size_edges=int(s[N.MESH_HOLES_STAT_LONG_EDGES]),
+                                blocked_edges=int(s[N.MESH_HOLES_STAT_BLOCKED_EDGES]), new_triangles=int(hdr["nT"]))
+
+
+def boundary_loops(mesh: TriangleMesh, max_size: int = 30, stream=None) -> dict:
+    """What :func:`close_holes` would do, as counts: ``boundary_edges``; ``closable_loops`` and the
+    ``closable_edges`` on them; ``open_by_size_edges``, the edges whose walk ran ``max_size`` steps
+    without coming back (a bounded walk cannot tell where a longer loop ends, so loops left open
+    by size are counted by their edges); ``blocked_edges``, those whose walk touched a blocked
+    vertex; ``new_triangles``.  ``max_size`` is limited to 3..64 on the device (``ValueError``)."""
+    return _holes_count(mesh, max_size, "boundary_loops", stream)[3]
+
+
+def close_holes(mesh: TriangleMesh, max_size: int = 30, return_record: bool = False, stream=None):
+    """Closes every hole of at most ``max_size`` edges.  The boundary edges ``B`` in ascending key
+    order, ``next(a, b)`` the boundary edge from ``b``; a vertex is blocked when its in or out
+    degree along ``B`` is not 1 or a directed triangle edge through it occurs twice; a loop of
+    ``3 <= L <= max_size`` edges without a blocked vertex is filled by ear clipping: ring
+    ``r[0..m-1]`` from the source of the loop's lowest edge in walk order, while ``m > 3`` the ``i``
+    with the smallest squared diagonal ``(dx dx + dy dy) + dz dz`` between ``r[i-1]`` and ``r[i+1]``
+    (ties to the lowest ``i``) gives ``(r[i+1], r[i], r[i-1])`` and leaves, last ``(r[2], r[1], r[0])``:
+    the winding of the fill is the reverse of the boundary's, so it agrees with its neighbours.
+    There is no self-intersection and no existing-edge check.  The input triangles come first,
+    unchanged, then the new ones in ascending (loop, clip step); vertices and densities are
+    unchanged, triangle normals are not carried over.  Our rule, MeshLab parity unpinned.
+    ``max_size`` is limited to 3..64 on the device (one wavefront per loop): ``ValueError`` otherwise."""
+    vert, tris, ws, rec = _holes_count(mesh, max_size, "close_holes", stream)
+    new = rec["new_triangles"]
+    out = tris
+    if new:
+        with torch.cuda.device(vert.device):
+            out = torch.empty((len(tris) + new, 3), dtype=torch.int32, device=vert.device)
+            out[:len(tris)].copy_(tris)
+            CL._raise(N.lib().slg_mesh_holes_emit(E._vp(vert), len(vert), len(tris), E._vp(ws), ws.numel(),
+                                                  out.data_ptr() + 12 * len(tris), new, E._stream(stream)))
+    closed = TriangleMesh(mesh.vertices, out, mesh.densities)
+    return (closed, rec) if return_record else closed
+
+
+def check_postprocess(params) -> None:
+    """What :func:`postprocess` takes of the reference's ``meshlab_params``: raises before any launch."""
+    _check_iterations(params.get("smooth_iters", 10), "postprocess")
+    if params.get("close_holes"):
+        check_hole_size(params.get("close_max_size", 30))
+    if params.get("simplify"):
+        raise NotImplementedError("simplify (quadric edge-collapse decimation) is a global priority queue and stays in the "
+                                  "reference (server/processing.py:778-781)")
+
+
+def postprocess(mesh: TriangleMesh, meshlab_params: dict, stream=None) -> TriangleMesh:
+    """The reference's MeshLab step (``server/processing.py:742-787``) on the device, in its order and
+    from its keys: ``smooth_type`` ("laplacian", anything else Taubin) with ``smooth_iters``
+    (default 10), then ``close_holes`` with ``close_max_size`` (default 30).  ``simplify`` raises
+    ``NotImplementedError``.  Our rules on the float64 mesh in memory; MeshLab parity unpinned."""
+    params = dict(meshlab_params or {})
+    check_postprocess(params)
+    iters = int(params.get("smooth_iters", 10))
+    if str(params.get("smooth_type", "taubin")) == "laplacian":
+        mesh = smooth_laplacian(mesh, iters, stream=stream)
+    else:
+        mesh = smooth_taubin(mesh, iters, stream=stream)
+    if params.get("close_holes"):
+        mesh = close_holes(mesh, int(params.get("close_max_size", 30)), stream=stream)
+    return mesh

@@ -688,7 +688,12 @@ class ProcessingLogic:
         pass, then ``mesh.poisson_grid`` at ``params["depth"]`` (default 10), the 0.02 density
         quantile trim and a binary STL.  The mesher is the dense grid's, so a depth
         above 10 raises ``ValueError``; ``mode="surface"`` (ball pivoting) raises
-        ``NotImplementedError``: it stays in the reference.  The MeshLab step is restated literally."""
+        ``NotImplementedError``: it stays in the reference.  The MeshLab step is restated literally
+        (it needs ``pymeshlab``) unless ``meshlab_params["backend"] == "device"``: then the STL is
+        written first as always, ``mesh.postprocess`` (smoothing and hole closing,
+        our rules) runs on the float64 mesh in memory and the file is overwritten.  MeshLab would
+        reload the STL's float32 vertices instead; ``simplify`` with this backend raises
+        ``NotImplementedError`` (``server/processing.py:778-781``) before anything is loaded."""
         from . import cloud as CL
         from . import mesh as MS
         if not os.path.exists(input_path):
@@ -702,6 +707,12 @@ class ProcessingLogic:
                                       "reference (server/processing.py:711-728)")
         else:
             raise ValueError(f"Unknown mode: {mode}")
+        backend = meshlab_params.get("backend", "pymeshlab") if meshlab_params and meshlab_params.get("enabled") else None
+        if backend not in (None, "pymeshlab", "device"):
+            raise ValueError(f"Unknown meshlab_params backend: {backend!r} (\"pymeshlab\" or \"device\")")
+        device_post = backend == "device"
+        if device_post:
+            MS.check_postprocess(meshlab_params)
         print(f"[Recon] Loading {input_path}...")
         pcd = CL.PointCloud.from_file(input_path)
         if not pcd.has_points():
@@ -733,7 +744,13 @@ class ProcessingLogic:
             raise ValueError("Generated mesh is empty.")
         print("[Recon] Computing normals and saving...")
         ProcessingLogic._write_mesh(mesh, output_path, "Recon")
-        if meshlab_params and meshlab_params.get("enabled"):
+        if device_post:
+            print("[MeshLab] Starting post-processing (device backend)...")
+            mesh = MS.postprocess(mesh, meshlab_params)
+            ProcessingLogic._write_mesh(mesh, output_path, "MeshLab")
+            print(f"[MeshLab] Post-processing complete. Final: {len(mesh.vertices)} vertices, "
+                  f"{len(mesh.triangles)} faces. Saved to {output_path}")
+        elif meshlab_params and meshlab_params.get("enabled"):
             print("[MeshLab] Starting post-processing...")
             try:
                 import pymeshlab

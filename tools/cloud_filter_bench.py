@@ -68,7 +68,12 @@ its stages, the 0.02 quantile trim, the triangle normals and the STL records.  I
 per-stage times, ``V``, ``T``, the cycles, the workspace, and the solve's rate against a byte model
 (per cycle and node of the finest level 4 sweeps and a residual at 24 B, 8 B for the restriction and
 16 B for the prolongation, times 8/7 for the coarser levels).  ``--mesh-only`` leaves every other
-step out.
+step out.  ``--post`` adds the mesh post-processing on the mesh trimmed at
+``--post-trim`` (default 0.02, the reference's; ``--post-punch K`` also drops every K-th vertex,
+since the trim of an open view removes nothing and leaves no hole): ``vertex_adjacency``, 10 Taubin iterations with
+that adjacency (20 passes), ``boundary_loops`` and ``close_holes`` at 30 edges.  It reports ``V``,
+``T``, the mean degree, the loop counts and the smoothing pass's rate against the byte model of a
+pass, ``V (24 (deg + 1) + 4 deg + 16 + 24)`` bytes with ``deg`` the mean row length used.
 
 Prints one JSON line.
 """
@@ -117,6 +122,10 @@ def main():
     ap.add_argument("--orient-only", action="store_true", help="with --orient: leave every other step out")
     ap.add_argument("--mesh", type=int, metavar="DEPTH", help="also time the watertight mesher at this depth")
     ap.add_argument("--mesh-only", action="store_true", help="with --mesh: leave every other step out")
+    ap.add_argument("--post", action="store_true", help="with --mesh: also time adjacency, Taubin smoothing and hole closing")
+    ap.add_argument("--post-trim", type=float, default=0.02, help="with --post: the density quantile trimmed before it")
+    ap.add_argument("--post-punch", type=int, default=0, metavar="K",
+                    help="with --post: also drop every K-th vertex (an open view's trim removes nothing, so this makes the holes)")
     args = ap.parse_args()
 
     import numpy as np
@@ -182,6 +191,55 @@ def main():
             "vertices_after_trim": len(trimmed.vertices), "triangles_after_trim": len(trimmed.triangles),
             "workspace_bytes": MS.workspace_bytes(depth, n),
             "solve_model_bytes": model, "solve_model_tb_per_s": model / (stage_ms["solve_ms"] * 1e-3) / 1e12}
+        if args.post:
+            if args.post_trim != 0.02:
+                trimmed = MS.remove_vertices_by_mask(mesh, mesh.densities < MS.quantile(mesh.densities, args.post_trim))
+            if args.post_punch > 0:
+                punch = (torch.arange(len(trimmed.vertices), device=trimmed.vertices.device) % args.post_punch) == args.post_punch // 2
+                trimmed = MS.remove_vertices_by_mask(trimmed, punch)
+            adj, ms_adj = timed(lambda: MS.vertex_adjacency(trimmed))
+            _, ms_tau = timed(lambda: MS.smooth_taubin(trimmed, 10, adjacency=adj))
+            loops, ms_loops = timed(lambda: MS.boundary_loops(trimmed, 30))
+            closed, ms_close = timed(lambda: MS.close_holes(trimmed, 30))
+            nv = len(trimmed.vertices)
+            nb = int(adj.boundary.sum().item())
+            # the rows the passes walk: the boundary row of a boundary vertex, the adjacency row otherwise
+            deg_rows = (adj.offsets[1:] - adj.offsets[:-1])[adj.boundary == 0].sum().item() + len(adj.boundary_neighbours)
+            deg = deg_rows / max(nv, 1)
+            pass_bytes = nv * (24 * (deg + 1) + 4 * deg + 16 + 24)
+            pass_ms = mean(ms_tau) / 20
+
+            def passes_alone(count=200):          # the launches back to back on two buffers: no clone, no allocation
+                lib, a, b = CL.N.lib(), trimmed.vertices.clone(), torch.empty_like(trimmed.vertices)
+                for _ in range(count):
+                    CL._raise(lib.slg_mesh_smooth_pass(E._vp(a), E._vp(b), nv, E._vp(adj.offsets), E._vp(adj.neighbours),
+                                                       E._vp(adj.boundary), E._vp(adj.boundary_offsets),
+                                                       E._vp(adj.boundary_neighbours), 1, 0.5, E._stream(None)))
+                    a, b = b, a
+
+            passes_alone(20)
+            torch.cuda.synchronize()
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            passes_alone(200)
+            t1.record()
+            t1.synchronize()
+            alone_ms = t0.elapsed_time(t1) / 200
+            res["mesh_post"] = {
+                "trim_quantile": args.post_trim, "punch_every": args.post_punch, "vertices": nv, "triangles": len(trimmed.triangles),
+                "adjacency_entries": len(adj.neighbours), "boundary_vertices": nb, "mean_row": deg,
+                "adjacency_ms": ms_adj, "taubin10_ms": ms_tau, "boundary_loops_ms": ms_loops, "close_holes_ms": ms_close,
+                "loops": loops, "triangles_after_close": len(closed.triangles),
+                "what_is_timed": "HIP events around each call with its allocations and header read-backs; taubin10 "
+                                 "includes the clone of the vertices and reuses the adjacency",
+                "pass_model_bytes": pass_bytes, "pass_ms": pass_ms,
+                "pass_model_tb_per_s": pass_bytes / (pass_ms * 1e-3) / 1e12 if pass_ms > 0 else None,
+                "pass_fraction_of_8_tb_per_s": pass_bytes / (pass_ms * 1e-3) / 8e12 if pass_ms > 0 else None,
+                "pass_alone_ms": alone_ms, "pass_alone_what": "200 launches back to back between two HIP events (includes one "
+                                                              "clone of the vertices), divided by 200",
+                "pass_alone_model_tb_per_s": pass_bytes / (alone_ms * 1e-3) / 1e12,
+                "pass_alone_compulsory_tb_per_s": nv * (48 + 4 * deg + 17) / (alone_ms * 1e-3) / 1e12}
+            del adj, closed
         del mesh, trimmed
         if args.mesh_only:
             print(json.dumps(res))
