@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import threading
 
 import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 
@@ -227,33 +228,42 @@ class NativeError(RuntimeError):
 
 
 _lib = None
+_lib_lock = threading.Lock()
 
 
 def lib():
-    """Load (once) and return the native library; raises if it was not built."""
+    """Load (once) and return the native library; raises if it was not built.  Threads that make
+    the first call together load it once: the handle is published only after its prototypes and
+    its provenance are set."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} missing: run `python -c 'import __graft_entry__ as g; "
-                              f"g.build()'` (hipcc --offload-arch=gfx950) first")
-        h = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in EXPORTS.items():
-            if AB_LIB is not None and not hasattr(h, name):
-                continue                     # an A/B build from an older tree (tools/ab.py)
-            fn = getattr(h, name)
-            fn.restype = res
-            fn.argtypes = args
-        if h.slg_version() != ABI_VERSION:
-            raise ImportError("libslgpu ABI version mismatch")
-        if AB_LIB is None:
-            # provenance: the product library must be the build of the sources beside it
-            from . import build as B
-            built, want = h.slg_build_id().decode(), B.BUILD_ID_PREFIX.decode() + B.source_digest()
-            if built != want:
-                raise ImportError(f"{LIB_PATH} was built from other sources ({built}, sources {want}): "
-                                  "rebuild it (__graft_entry__.build())")
-        _lib = h
+        with _lib_lock:
+            if _lib is None:
+                _lib = _load()
     return _lib
+
+
+def _load():
+    if not os.path.exists(LIB_PATH):
+        raise ImportError(f"{LIB_PATH} missing: run `python -c 'import __graft_entry__ as g; "
+                          f"g.build()'` (hipcc --offload-arch=gfx950) first")
+    h = ctypes.CDLL(LIB_PATH)
+    for name, (res, args) in EXPORTS.items():
+        if AB_LIB is not None and not hasattr(h, name):
+            continue                     # an A/B build from an older tree (tools/ab.py)
+        fn = getattr(h, name)
+        fn.restype = res
+        fn.argtypes = args
+    if h.slg_version() != ABI_VERSION:
+        raise ImportError("libslgpu ABI version mismatch")
+    if AB_LIB is None:
+        # provenance: the product library must be the build of the sources beside it
+        from . import build as B
+        built, want = h.slg_build_id().decode(), B.BUILD_ID_PREFIX.decode() + B.source_digest()
+        if built != want:
+            raise ImportError(f"{LIB_PATH} was built from other sources ({built}, sources {want}): "
+                              "rebuild it (__graft_entry__.build())")
+    return h
 
 
 def kernel_table() -> dict:

@@ -32,6 +32,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
+import threading
 
 import numpy as np
 import torch
@@ -198,18 +199,30 @@ def _nonempty(pc) -> PointCloud:
 
 
 # ----------------------------------------------------------------------------- filters
-_WS: dict = {}
+_WS = threading.local()     # .by_device: the calling thread's workspace per device
+
+
+def _workspaces() -> dict:
+    """``{device: workspace}`` of the calling thread.  A step's kernels keep the grid, the status
+    word and, between the calls of a multi-call step, its state in the workspace, and the wrappers
+    run with the GIL released: a workspace is never shared between threads, and ends with its
+    thread."""
+    by_device = getattr(_WS, "by_device", None)
+    if by_device is None:
+        by_device = _WS.by_device = {}
+    return by_device
 
 
 def _workspace(device, need) -> torch.Tensor:
-    """The device's workspace, grown to ``need`` bytes (what the step's ``slg_*_ws_bytes`` returned;
-    a negative size is that call's error code)."""
+    """The calling thread's workspace on the device, grown to ``need`` bytes (what the step's
+    ``slg_*_ws_bytes`` returned; a negative size is that call's error code)."""
     need = int(need)
     if need < 0:
         N.check(-need)
-    ws = _WS.get(device)
+    by_device = _workspaces()
+    ws = by_device.get(device)
     if ws is None or ws.numel() < need:
-        ws = _WS[device] = torch.empty(need, dtype=torch.uint8, device=device)
+        ws = by_device[device] = torch.empty(need, dtype=torch.uint8, device=device)
     return ws
 
 
@@ -234,11 +247,11 @@ def _check_status(ws: torch.Tensor, what: str) -> None:
 
 
 def far_count(device) -> int:
-    """Points the last :func:`statistical_mask` or :func:`normal_covariances` on ``device`` sent
-    to the whole-cloud kernel (the ring walk reached its cap): the int32 at byte 8 of the
-    workspace.  After :func:`registration_icp` or :func:`evaluate_registration`: the source points
-    sent to the whole-target kernel, summed over the evaluations.  A test hook."""
-    return int(_WS[device][8:12].view(torch.int32).item())
+    """Points the calling thread's last :func:`statistical_mask` or :func:`normal_covariances` on
+    ``device`` sent to the whole-cloud kernel (the ring walk reached its cap): the int32 at byte 8
+    of that thread's workspace.  After :func:`registration_icp` or :func:`evaluate_registration`:
+    the source points sent to the whole-target kernel, summed over the evaluations.  A test hook."""
+    return int(_workspaces()[device][8:12].view(torch.int32).item())
 
 
 def _filter_ws(xyz: torch.Tensor, k: int):

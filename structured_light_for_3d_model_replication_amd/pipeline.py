@@ -199,6 +199,7 @@ def plan_split(n_folders: int, frames_per_folder: int, frame_mb: float, threads:
 
 
 _DECODE_STREAMS: dict = {}
+_DECODE_STREAMS_LOCK = threading.Lock()
 PNG_WAVES_PER_CU = 3        # png_inflate_kernel: one 64-lane wave per stream, ~50 KB of LDS each
 
 
@@ -233,15 +234,16 @@ def png_decode_stream(device: int | None = None, n_streams: int | None = None):
     waves hold); a plain stream when the mask cannot be set."""
     dev = torch.cuda.current_device() if device is None else int(device)
     every = png_reserve_every(n_streams, torch.cuda.get_device_properties(dev).multi_processor_count)
-    s = _DECODE_STREAMS.get((dev, every))
-    if s is None:
-        h = ctypes.c_void_p()
-        with torch.cuda.device(dev):
-            if every >= 2 and N.lib().slg_stream_create_reserving(every, ctypes.byref(h)) == 0:
-                s = torch.cuda.ExternalStream(h.value, device=torch.device("cuda", dev))
-            else:
-                s = torch.cuda.Stream(device=dev)
-        _DECODE_STREAMS[(dev, every)] = s
+    with _DECODE_STREAMS_LOCK:                       # one stream per key, whoever asks first
+        s = _DECODE_STREAMS.get((dev, every))
+        if s is None:
+            h = ctypes.c_void_p()
+            with torch.cuda.device(dev):
+                if every >= 2 and N.lib().slg_stream_create_reserving(every, ctypes.byref(h)) == 0:
+                    s = torch.cuda.ExternalStream(h.value, device=torch.device("cuda", dev))
+                else:
+                    s = torch.cuda.Stream(device=dev)
+            _DECODE_STREAMS[(dev, every)] = s
     return s
 
 
@@ -646,7 +648,10 @@ class PipelineStats:
                 "split": self.split}
 
 
-LAST_STATS: PipelineStats | None = None     # the stats of the last BatchPipeline.run (tools/e2e_files.py)
+# The stats of the last BatchPipeline.run (tools/e2e_files.py).  Batch mode takes one caller at a
+# time: with two runs at once this names whichever started last; each pipeline's own
+# ``stats`` attribute stays its own.
+LAST_STATS: PipelineStats | None = None
 
 
 class BatchPipeline:

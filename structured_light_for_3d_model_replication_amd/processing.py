@@ -21,6 +21,7 @@ from __future__ import annotations
 import collections
 import glob
 import os
+import threading
 
 import numpy as np
 import torch
@@ -29,16 +30,23 @@ from . import engine as E
 from . import frames as FR
 from . import ply as PLY
 
-_ENGINES: dict = {}
+_TLS = threading.local()                    # .engines: this thread's Reconstructors
 _CALIBS: "collections.OrderedDict" = collections.OrderedDict()
+_CALIBS_LOCK = threading.Lock()
 _CALIBS_MAX = 4
 
 
 def _engine(h, w):
+    """The calling thread's engine for one geometry on the current GPU.  An engine owns a
+    workspace that ``slg_decode_stats`` arms for the launch after it, so no two threads may share
+    one: each thread gets its own, freed with the thread."""
+    engines = getattr(_TLS, "engines", None)
+    if engines is None:
+        engines = _TLS.engines = {}
     key = (h, w, torch.cuda.current_device())
-    if key not in _ENGINES:
-        _ENGINES[key] = E.Reconstructor(h, w)
-    return _ENGINES[key]
+    if key not in engines:
+        engines[key] = E.Reconstructor(h, w)
+    return engines[key]
 
 
 def _hasher():
@@ -109,25 +117,30 @@ def _device_calib(calib, h, w):
     with another ``Nc`` object (e.g. the same ``.mat`` loaded again) is confirmed by the full
     digest of its ``Nc`` against the one taken when the entry was made; a mismatch replaces the
     entry.  (An in-place edit of ``Nc`` entries outside the sample, on the same object, is not
-    seen: edit a copy.)"""
+    seen: edit a copy.)
+
+    Threads share the cache: a ``DeviceCalib`` is only read on the device, and its constructor
+    returns with the upload finished.  One lock covers the lookup, the upload, the insert and the
+    eviction, so two threads that miss on one calibration upload it once."""
     key = (torch.cuda.current_device(), h, w, calib_fingerprint(calib))
     nc = calib.get("Nc") if hasattr(calib, "get") else None
-    ent = _CALIBS.get(key)
-    if ent is not None:
-        dc, ref, full = ent
-        if nc is not None and ref is not None and ref() is nc:
-            _CALIBS.move_to_end(key)
-            return dc
-        if calib_fingerprint(calib, full=True) == full:
-            _CALIBS[key] = (dc, _ref(nc), full)
-            _CALIBS.move_to_end(key)
-            return dc
-    dc = E.DeviceCalib(calib, h, w)
-    _CALIBS[key] = (dc, _ref(nc), calib_fingerprint(calib, full=True))
-    _CALIBS.move_to_end(key)
-    while len(_CALIBS) > _CALIBS_MAX:
-        _CALIBS.popitem(last=False)
-    return dc
+    with _CALIBS_LOCK:
+        ent = _CALIBS.get(key)
+        if ent is not None:
+            dc, ref, full = ent
+            if nc is not None and ref is not None and ref() is nc:
+                _CALIBS.move_to_end(key)
+                return dc
+            if calib_fingerprint(calib, full=True) == full:
+                _CALIBS[key] = (dc, _ref(nc), full)
+                _CALIBS.move_to_end(key)
+                return dc
+        dc = E.DeviceCalib(calib, h, w)
+        _CALIBS[key] = (dc, _ref(nc), calib_fingerprint(calib, full=True))
+        _CALIBS.move_to_end(key)
+        while len(_CALIBS) > _CALIBS_MAX:
+            _CALIBS.popitem(last=False)
+        return dc
 
 
 def _needed_frames(n_files, cfg: E.DecodeConfig):
