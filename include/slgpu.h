@@ -912,6 +912,55 @@ int32_t slg_mesh_holes_count(const int32_t *triangles, int64_t n_triangles, int6
 int32_t slg_mesh_holes_emit(const double *vertices, int64_t n_vertices, int64_t n_triangles, void *ws,
                             int64_t ws_bytes, int32_t *triangles_out, int64_t n_new_triangles, void *stream);
 
+/* ---- Mesh decimation (csrc/cloud_decimate.hip): quadric edge collapse in rounds of
+ * independent collapses, what the device takes of meshlab_params["simplify"]
+ * (server/processing.py:778-781).  Our rule, MeshLab / VCGlib parity unpinned; a pure function of
+ * the mesh and the target, restated in tests/decimate_ref.py.  Asynchronous on `stream`.
+ *
+ * One workspace of slg_mesh_decimate_ws_bytes(V, T) bytes, 256-byte aligned, carries the state
+ * from init through the rounds to emit.  It begins with the mesh header: int32 status at byte 0
+ * (SLG_FILTER_BAD_INDEX: a triangle index outside 0..V-1; every later kernel then returns), int64
+ * alive vertices at 8, alive triangles at 16, the last round's candidate edges at 24 and applied
+ * collapses at 32, all collapses since init at 40, and int64 stats[8] at 128
+ * (SLG_MESH_DECIMATE_STAT_* of the last round).
+ *
+ *   slg_mesh_decimate_init   copies positions and triangles into the workspace, builds the
+ *                        incidence CSR and sums every vertex's quadric over its triangles in
+ *                        ascending index: K = (a2, ab, ac, ad, b2, bc, bd, c2, cd, d2) of
+ *                        n = (B - A) x (C - A), not normalised, d = -((nx Ax + ny Ay) + nz Az).
+ *   slg_mesh_decimate_round  one round on the n_alive triangles the header reports (the caller
+ *                        reads it after every round): adjacency, the candidate edges u < v in
+ *                        ascending key, their refusals (boundary, nonmanifold, link, valence, nan,
+ *                        flip), placement and cost, the rank by (cost bits, key),
+ *                        SLG_MESH_DECIMATE_SWEEPS selection sweeps by integer atomicMin over the
+ *                        closed neighbourhoods, and the first ceil((n_alive - target) / 2) selected
+ *                        in rank order applied: P[u] = p, Q[u] += Q[v], v -> u, triangles with two
+ *                        equal corners dropped, the rest compacted in order.
+ *   slg_mesh_decimate_emit   the surviving vertices (and densities, when given) in their order
+ *                        and the alive triangles renumbered: n_vertices_out = header's alive
+ *                        vertices, n_triangles_out = alive triangles.
+ *
+ * SLG_ERR_INVALID for a NULL or misaligned buffer, V or T <= 0, V >= 2^31, 3 T > 2^30, n_alive
+ * outside 1..T, a target below 0 or not below n_alive, or a workspace that is too small. */
+#define SLG_MESH_DECIMATE_SWEEPS 4
+#define SLG_MESH_DECIMATE_STAT_BOUNDARY 0    /* both endpoints on the boundary */
+#define SLG_MESH_DECIMATE_STAT_NONMANIFOLD 1 /* (u, v) or (v, u) not exactly once among the winding pairs */
+#define SLG_MESH_DECIMATE_STAT_LINK 2        /* the endpoints share other than two neighbours */
+#define SLG_MESH_DECIMATE_STAT_VALENCE 3     /* a shared neighbour of valence below 4 */
+#define SLG_MESH_DECIMATE_STAT_FLIP 4        /* a triangle around the edge would turn over */
+#define SLG_MESH_DECIMATE_STAT_NAN 5         /* the placement's cost is not finite */
+#define SLG_MESH_DECIMATE_STAT_VALID 6       /* candidates that passed every test */
+#define SLG_MESH_DECIMATE_STAT_SELECTED 7    /* selected by the sweeps (the budget may apply fewer) */
+int64_t slg_mesh_decimate_ws_bytes(int64_t n_vertices, int64_t n_triangles);
+int32_t slg_mesh_decimate_init(const double *vertices, int64_t n_vertices, const int32_t *triangles,
+                               int64_t n_triangles, void *ws, int64_t ws_bytes, void *stream);
+int32_t slg_mesh_decimate_round(void *ws, int64_t ws_bytes, int64_t n_vertices, int64_t n_triangles,
+                                int64_t n_alive, int64_t target, void *stream);
+int32_t slg_mesh_decimate_emit(void *ws, int64_t ws_bytes, int64_t n_vertices, int64_t n_triangles,
+                               const double *densities, double *vertices_out, double *densities_out,
+                               int64_t n_vertices_out, int32_t *triangles_out, int64_t n_triangles_out,
+                               void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -194,6 +194,10 @@ EXPORTS = {
     "slg_mesh_smooth_pass": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_dbl, c_vp]),
     "slg_mesh_holes_count": (c_i32, [c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp]),
     "slg_mesh_holes_emit": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "slg_mesh_decimate_ws_bytes": (c_i64, [c_i64, c_i64]),
+    "slg_mesh_decimate_init": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "slg_mesh_decimate_round": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp]),
+    "slg_mesh_decimate_emit": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
 }
 MESH_HDR_BYTES, MESH_MAX_DEPTH = 256, 10         # SLG_MESH_HDR_BYTES; kMaxDepth of csrc/cloud_mesh.hip
 # SLG_MESH_WS_*: the stages of slg_mesh_ws_bytes
@@ -205,6 +209,9 @@ MESH_HOLES_MAX_SIZE = 64                         # SLG_MESH_HOLES_MAX_SIZE
 # SLG_MESH_HOLES_STAT_*: indices into the header's stats after slg_mesh_holes_count
 (MESH_HOLES_STAT_EDGES, MESH_HOLES_STAT_LOOPS, MESH_HOLES_STAT_CLOSABLE_EDGES, MESH_HOLES_STAT_LONG_EDGES,
  MESH_HOLES_STAT_BLOCKED_EDGES) = range(5)
+MESH_DECIMATE_SWEEPS = 4                         # SLG_MESH_DECIMATE_SWEEPS
+# SLG_MESH_DECIMATE_STAT_*: the last round's counts in the header's stats (csrc/cloud_decimate.hip)
+MESH_DECIMATE_STATS = ("boundary", "nonmanifold", "link", "valence", "flip", "nan", "valid", "selected")
 ORIENT_MAX_K, ORIENT_STATS_LEN = 128, 128        # SLG_ORIENT_MAX_K, SLG_ORIENT_STATS_LEN
 # SLG_ORIENT_STAT_*: indices into the stats of slg_emst / slg_orient_tangent
 (ORIENT_STAT_EMST_ROUNDS, ORIENT_STAT_TREE_ROUNDS, ORIENT_STAT_LIST_FAR, ORIENT_STAT_WALKED, ORIENT_STAT_FAR,

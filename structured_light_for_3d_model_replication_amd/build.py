@@ -32,6 +32,7 @@ SRCS = [os.path.join(CSRC, n) for n in ("slgpu.hip", "stats.hip", "ply.hip", "co
                                         "cloud_grid.hip", "cloud_filter.hip", "cloud_cluster.hip",
                                         "cloud_normals.hip", "cloud_icp.hip", "cloud_feature.hip",
                                         "cloud_ransac.hip", "cloud_plane.hip", "cloud_orient.hip", "cloud_mesh.hip", "cloud_meshpost.hip",
+                                        "cloud_decimate.hip",
                                         "code_object.cpp",
                                         "png_gray.cpp",
                                         "gather.cpp")]

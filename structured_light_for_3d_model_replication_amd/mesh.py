@@ -13,7 +13,8 @@ the device equals it bit for bit.  Node fields are float64 ``[R+1, R+1, R+1]`` t
 Behind it, what the device takes of the reference's MeshLab step (``csrc/cloud_meshpost.hip``,
 DESIGN.md §17): :func:`vertex_adjacency`, :func:`smooth_laplacian`, :func:`smooth_taubin`,
 :func:`close_holes`, :func:`boundary_loops` and :func:`postprocess`, restated in
-``tests/meshpost_ref.py``; parity with MeshLab / VCGlib is unpinned.
+``tests/meshpost_ref.py``, and :func:`decimate_quadric` (``csrc/cloud_decimate.hip``),
+restated in ``tests/decimate_ref.py``; parity with MeshLab / VCGlib is unpinned.
 """
 from __future__ import annotations
 
@@ -350,7 +351,7 @@ def read_stl(path):
 # What the device takes of the reference's MeshLab step (server/processing.py:742-787): vertex
 # adjacency, Laplacian / Taubin smoothing and hole closing (csrc/cloud_meshpost.hip).  Our rules,
 # restated in tests/meshpost_ref.py and equal to it bit for bit; parity with MeshLab / VCGlib is
-# unpinned.  Quadric edge-collapse decimation stays in the reference.
+# unpinned.  Quadric edge-collapse decimation follows further down.
 _POST_HDR = np.dtype([("status", "<i4"), ("R", "<i4"), ("nV", "<i8"), ("nT", "<i8"), ("unused", "<f8", 13),
                       ("stats", "<i8", 8)])
 MIN_HOLE_SIZE, MAX_HOLE_SIZE = 3, N.MESH_HOLES_MAX_SIZE
@@ -555,21 +556,137 @@ def close_holes(mesh: TriangleMesh, max_size: int = 30, return_record: bool = Fa
     return (closed, rec) if return_record else closed
 
 
+# ----------------------------------------------------------------------------- decimation
+# Quadric edge collapse in rounds of independent collapses (csrc/cloud_decimate.hip): our rule,
+# restated in tests/decimate_ref.py and equal to it bit for bit; parity with MeshLab / VCGlib is
+# unpinned.
+DECIMATE_SWEEPS = N.MESH_DECIMATE_SWEEPS
+DEFAULT_TARGET_FACES = 50000
+_DEC_HDR = np.dtype([("status", "<i4"), ("R", "<i4"), ("nV", "<i8"), ("nT", "<i8"), ("nC", "<i8"), ("applied", "<i8"),
+                     ("total", "<i8"), ("unused", "<f8", 10), ("stats", "<i8", 8)])
+
+
+def check_target_faces(target, what: str = "decimate_quadric") -> int:
+    """``target`` as an int when it is a whole number >= 0, else ``ValueError``."""
+    try:
+        whole = not isinstance(target, bool) and float(target) == int(target)
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole or int(target) < 0:
+        raise ValueError(f"{what}: target_faces must be a whole number >= 0, not {target!r}")
+    return int(target)
+
+
+def decimate_quadric(mesh: TriangleMesh, target_faces, max_rounds: int = 512, return_record: bool = False, stream=None,
+                     timings=None):
+    """Quadric edge-collapse decimation to ``target_faces`` triangles, in rounds of independent
+    collapses.  Every vertex carries the sum of its triangles' plane quadrics (weight (2 area)^2);
+    a round builds the adjacency, refuses the candidate edges ``u < v`` that have both ends on the
+    boundary, are not shared by exactly two consistently wound triangles, whose ends share other
+    than two neighbours or one of valence below 4, whose placement costs a non-finite amount or
+    turns a triangle over; places the rest (a boundary end stays put; else the cheapest of the
+    quadric's minimiser when it lies within two edge lengths of the midpoint, ``P[u]``, ``P[v]`` and
+    the midpoint, ties to the earliest), ranks them by (cost bits, key), selects in
+    ``DECIMATE_SWEEPS`` sweeps those that hold the lowest rank on every vertex of their closed
+    neighbourhood, and applies the first ``ceil((T - target) / 2)`` of them in rank order: ``u``
+    moves to the placement and takes ``Q[u] + Q[v]``, ``v`` leaves, each collapse removes two
+    triangles.  It stops at the target (``T_out`` is ``target`` or ``target - 1``), when no edge is
+    valid, or after ``max_rounds`` rounds.  Boundary vertices never move.  A pure function of the
+    mesh and the target; our rule, MeshLab parity unpinned.
+
+    A new mesh: the vertices a collapse removed are dropped, all others keep their order (and
+    ``densities``), triangles keep their order and are renumbered, ``triangle_normals`` is ``None``.
+    With ``return_record`` also a dict: ``faces_in``, ``faces_out``, ``rounds``, ``collapses``,
+    ``stop`` ("target", "no_valid_edge" or "max_rounds") and the last round's counts ``boundary``,
+    ``nonmanifold``, ``link``, ``valence``, ``flip``, ``nan``, ``valid``, ``selected``.
+    ``ValueError`` for a target that is no whole number >= 0 or ``max_rounds < 0``, ``IndexError``
+    for a triangle index outside ``0 .. V - 1``.  ``timings``: a list that gets one dict per round
+    (``triangles`` and ``candidates`` going in, ``valid``, ``applied``, and ``ms`` by HIP events
+    around the round and its header read-back)."""
+    target = check_target_faces(target_faces)
+    if isinstance(max_rounds, float) and not max_rounds.is_integer() or int(max_rounds) < 0:
+        raise ValueError(f"decimate_quadric: max_rounds must be a whole number >= 0, not {max_rounds}")
+    max_rounds = int(max_rounds)
+    vert, tris = _post_mesh(mesh, "decimate_quadric")
+    nv, nt, dev = len(vert), len(tris), vert.device
+    rec = dict(faces_in=nt, faces_out=nt, rounds=0, collapses=0, stop="target", **{k: 0 for k in N.MESH_DECIMATE_STATS})
+    if nv == 0 or nt == 0:
+        out = TriangleMesh(vert.clone(), tris.clone(), None if mesh.densities is None else mesh.densities.clone())
+        return (out, rec) if return_record else out
+    dens = None if mesh.densities is None else mesh.densities.contiguous()
+    lib, st = N.lib(), E._stream(stream)
+    with torch.cuda.device(dev):
+        need = int(lib.slg_mesh_decimate_ws_bytes(nv, nt))
+        if need < 0:
+            CL._raise(-need)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+
+        def header():
+            hdr = np.frombuffer(ws[:_DEC_HDR.itemsize].cpu().numpy().tobytes(), dtype=_DEC_HDR)[0]
+            if int(hdr["status"]) & N.FILTER_BAD_INDEX:
+                raise IndexError("decimate_quadric: a triangle index lies outside 0 .. V - 1")
+            return hdr
+
+        CL._raise(lib.slg_mesh_decimate_init(E._vp(vert), nv, E._vp(tris), nt, E._vp(ws), ws.numel(), st))
+        hdr = header()
+        alive = nt
+        while True:
+            if alive <= target:
+                rec["stop"] = "target"
+                break
+            if rec["rounds"] >= max_rounds:
+                rec["stop"] = "max_rounds"
+                break
+            marks = _Stages({} if timings is not None else None, stream)
+            marks.mark("start")
+            CL._raise(lib.slg_mesh_decimate_round(E._vp(ws), ws.numel(), nv, nt, alive, target, st))
+            hdr = header()                     # the one read-back per round: the next round's size, and whether there is one
+            marks.mark("round")
+            marks.close()
+            rec["rounds"] += 1
+            rec.update({k: int(hdr["stats"][i]) for i, k in enumerate(N.MESH_DECIMATE_STATS)})
+            if timings is not None:
+                timings.append(dict(triangles=alive, candidates=int(hdr["nC"]), valid=rec["valid"], applied=int(hdr["applied"]),
+                                    ms=marks.timings["round_ms"]))
+            alive = int(hdr["nT"])
+            if int(hdr["applied"]) == 0:
+                rec["stop"] = "no_valid_edge"
+                break
+        kv = int(hdr["nV"])
+        rec.update(faces_out=alive, collapses=int(hdr["total"]))
+        v_out = torch.empty((kv, 3), dtype=torch.float64, device=dev)
+        t_out = torch.empty((alive, 3), dtype=torch.int32, device=dev)
+        d_out = torch.empty(kv, dtype=torch.float64, device=dev) if dens is not None else None
+        CL._raise(lib.slg_mesh_decimate_emit(E._vp(ws), ws.numel(), nv, nt, E._vp(dens), E._vp(v_out), E._vp(d_out), kv,
+                                             E._vp(t_out), alive, st))
+    out = TriangleMesh(v_out, t_out, d_out)
+    return (out, rec) if return_record else out
+
+
 def check_postprocess(params) -> None:
     """What :func:`postprocess` takes of the reference's ``meshlab_params``: raises before any launch."""
     _check_iterations(params.get("smooth_iters", 10), "postprocess")
     if params.get("close_holes"):
         check_hole_size(params.get("close_max_size", 30))
     if params.get("simplify"):
-        raise NotImplementedError("simplify (quadric edge-collapse decimation) is a global priority queue and stays in the "
-                                  "reference (server/processing.py:778-781)")
+        rule = params.get("simplify_rule")
+        if rule is None:
+            raise NotImplementedError("simplify (quadric edge-collapse decimation) is a global priority queue and stays in the "
+                                      "reference (server/processing.py:778-781); \"simplify_rule\": \"rounds\" asks for the "
+                                      "device's own rule instead (mesh.decimate_quadric)")
+        if rule != "rounds":
+            raise ValueError(f"postprocess: unknown simplify_rule {rule!r} (\"rounds\": mesh.decimate_quadric)")
+        check_target_faces(params.get("target_faces", DEFAULT_TARGET_FACES), "postprocess")
 
 
 def postprocess(mesh: TriangleMesh, meshlab_params: dict, stream=None) -> TriangleMesh:
     """The reference's MeshLab step (``server/processing.py:742-787``) on the device, in its order and
     from its keys: ``smooth_type`` ("laplacian", anything else Taubin) with ``smooth_iters``
-    (default 10), then ``close_holes`` with ``close_max_size`` (default 30).  ``simplify`` raises
-    ``NotImplementedError``.  Our rules on the float64 mesh in memory; MeshLab parity unpinned."""
+    (default 10), then ``close_holes`` with ``close_max_size`` (default 30), then ``simplify`` with
+    ``"simplify_rule": "rounds"``: :func:`decimate_quadric` to ``target_faces`` (default 50,000).
+    ``simplify`` alone names MeshLab's sequential queue, which is another rule, and raises
+    ``NotImplementedError``; any other ``simplify_rule`` is a ``ValueError``.  Our rules on the
+    float64 mesh in memory; MeshLab parity unpinned."""
     params = dict(meshlab_params or {})
     check_postprocess(params)
     iters = int(params.get("smooth_iters", 10))
@@ -579,4 +696,6 @@ def postprocess(mesh: TriangleMesh, meshlab_params: dict, stream=None) -> Triang
         mesh = smooth_taubin(mesh, iters, stream=stream)
     if params.get("close_holes"):
         mesh = close_holes(mesh, int(params.get("close_max_size", 30)), stream=stream)
+    if params.get("simplify"):
+        mesh = decimate_quadric(mesh, int(params.get("target_faces", DEFAULT_TARGET_FACES)), stream=stream)
     return mesh

@@ -705,8 +705,12 @@ class ProcessingLogic:
         (it needs ``pymeshlab``) unless ``meshlab_params["backend"] == "device"``: then the STL is
         written first as always, ``mesh.postprocess`` (smoothing and hole closing,
         our rules) runs on the float64 mesh in memory and the file is overwritten.  MeshLab would
-        reload the STL's float32 vertices instead; ``simplify`` with this backend raises
-        ``NotImplementedError`` (``server/processing.py:778-781``) before anything is loaded."""
+        reload the STL's float32 vertices instead.  ``simplify`` with this backend and
+        ``"simplify_rule": "rounds"`` runs ``mesh.decimate_quadric`` to ``target_faces`` (default
+        50,000) after the hole closing (quadric edge collapse in independent rounds,
+        our rule and not MeshLab's sequential queue); ``simplify`` without that key raises
+        ``NotImplementedError`` (``server/processing.py:778-781``), any other rule or a bad
+        ``target_faces`` ``ValueError``, all before anything is loaded."""
         from . import cloud as CL
         from . import mesh as MS
         if not os.path.exists(input_path):

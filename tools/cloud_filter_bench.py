@@ -74,6 +74,14 @@ since the trim of an open view removes nothing and leaves no hole): ``vertex_adj
 that adjacency (20 passes), ``boundary_loops`` and ``close_holes`` at 30 edges.  It reports ``V``,
 ``T``, the mean degree, the loop counts and the smoothing pass's rate against the byte model of a
 pass, ``V (24 (deg + 1) + 4 deg + 16 + 24)`` bytes with ``deg`` the mean row length used.
+``--decimate TARGET`` (with ``--post``) adds ``mesh.decimate_quadric`` of the
+hole-closed mesh to ``TARGET`` faces: per-call time, rounds, collapses, the stop reason, ``V`` and
+``T`` in and out, the time of every round, and the byte model of the candidate evaluation summed
+over the rounds, ``candidates (350 + 192 deg)`` bytes with ``deg`` the mean valence (per edge two
+neighbour and two incidence rows with their triangles' corners and positions, two quadrics, the
+outputs), beside its compulsory traffic.  ``--kernel-stats CSV`` takes a ``rocprofv3 --kernel-trace
+--stats`` kernel table of a run of this very command and reports the evaluation kernel's time per
+call and its rate against the model.
 
 Prints one JSON line.
 """
@@ -126,6 +134,8 @@ def main():
     ap.add_argument("--post-trim", type=float, default=0.02, help="with --post: the density quantile trimmed before it")
     ap.add_argument("--post-punch", type=int, default=0, metavar="K",
                     help="with --post: also drop every K-th vertex (an open view's trim removes nothing, so this makes the holes)")
+    ap.add_argument("--decimate", type=int, metavar="TARGET", help="with --post: also time decimate_quadric to this many faces")
+    ap.add_argument("--kernel-stats", metavar="CSV", help="with --decimate: rocprofv3's kernel stats of a run of this command")
     args = ap.parse_args()
 
     import numpy as np
@@ -239,6 +249,40 @@ def main():
                                                               "clone of the vertices), divided by 200",
                 "pass_alone_model_tb_per_s": pass_bytes / (alone_ms * 1e-3) / 1e12,
                 "pass_alone_compulsory_tb_per_s": nv * (48 + 4 * deg + 17) / (alone_ms * 1e-3) / 1e12}
+            if args.decimate is not None:
+                rounds = []
+
+                def run_dec():
+                    rounds.clear()
+                    return MS.decimate_quadric(closed, args.decimate, return_record=True, timings=rounds)
+
+                (small, rec), ms_dec = timed(run_dec)
+                print(f"[device] decimate_quadric done {ms_dec}", file=sys.stderr, flush=True)
+                vin, tin = len(closed.vertices), len(closed.triangles)
+                deg_all = len(adj.neighbours) / max(nv, 1)
+                cands = sum(r["candidates"] for r in rounds)
+                model = cands * (350 + 192 * deg_all)
+                # read once: per vertex position, quadric, two offsets and the flag; per triangle its corners and
+                # three incidence and three winding keys; per edge the key, two neighbour entries and the outputs
+                compulsory = sum(r["triangles"] * (121 / 2 + 12 + 48) + r["candidates"] * (8 + 8 + 36) for r in rounds)
+                dec = {"target": args.decimate, "vertices_in": vin, "triangles_in": tin, "vertices_out": len(small.vertices),
+                       "triangles_out": len(small.triangles), "record": rec, "device_ms": ms_dec,
+                       "what_is_timed": "HIP events around decimate_quadric with its allocations, one header read-back "
+                                        "per round and the emit; rounds: the last call's, each round with its read-back",
+                       "rounds": rounds, "round_first_ms": rounds[0]["ms"] if rounds else None,
+                       "round_last_ms": rounds[-1]["ms"] if rounds else None,
+                       "workspace_bytes": int(CL.N.lib().slg_mesh_decimate_ws_bytes(vin, tin)), "mean_valence": deg_all,
+                       "eval_candidates_all_rounds": cands, "eval_model_bytes": model, "eval_compulsory_bytes": compulsory}
+                if args.kernel_stats:
+                    import csv
+                    rows = [r for r in csv.DictReader(open(args.kernel_stats)) if "evaluate_kernel" in r.get("Name", "")]
+                    calls = args.warmup + args.steps
+                    if rows:
+                        eval_ms = sum(float(r["TotalDurationNs"]) for r in rows) / calls * 1e-6
+                        dec.update(eval_kernel_ms_per_call=eval_ms, eval_model_tb_per_s=model / (eval_ms * 1e-3) / 1e12,
+                                   eval_compulsory_tb_per_s=compulsory / (eval_ms * 1e-3) / 1e12)
+                res["mesh_decimate"] = dec
+                del small
             del adj, closed
         del mesh, trimmed
         if args.mesh_only:
