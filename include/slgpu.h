@@ -35,6 +35,19 @@
  *   - All buffer pointers are DEVICE pointers owned by the caller (the library never
  *     allocates or frees caller memory); scratch lives in a caller-provided workspace of
  *     slg_workspace_bytes() bytes, zeroed once with slg_workspace_init().
+ *   - No call depends on what its memory held before.  Every other workspace (the cloud steps'
+ *     `ws`, the mesher's, the post-processing, decimation, PLY and PNG ones, the PNG `raw` scratch)
+ *     and every output buffer is NOT initialised by the caller: a call writes what it later reads,
+ *     clears on its own stream what its kernels accumulate into, and writes every entry of an
+ *     output it documents (a prefix of `count` entries where it says so; what lies behind the
+ *     prefix is unspecified).  The result is a pure function of the inputs whatever the bytes
+ *     were: zeros, 0xFF, or another call's leftovers at another size.  The two exceptions: the
+ *     per-view fused workspace above (zeroed once by slg_workspace_init, never by a call), and
+ *     the arena cursor of slg_workspace_set_arena (the caller's counter, which the launches
+ *     advance).  A step made of several calls (slg_ransac_prepare -> slg_ransac_batch,
+ *     slg_plane_batch -> slg_plane_finish, the mesher's stages, count -> emit of the adjacency
+ *     and of the holes, decimate init -> round -> emit) keeps its state in the workspace between
+ *     its own calls: the workspace is free only before the first of them.
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream).  Every export only
  *     enqueues work (no host synchronisation), so calls can be captured into a hipGraph.
  *   - Return value: SLG_OK (0) or an SLG_ERR_* code; slg_last_error() returns a thread-local
@@ -559,7 +572,7 @@ int32_t slg_cloud_centroid(const double *xyz, int64_t n, void *ws, int64_t ws_by
  * byte 8 counts the queries, over all evaluations, that left the grid walk for the whole-target
  * kernel.  init_T is HOST float64 [16] like T above.  result_out is DEVICE float64
  * [SLG_ICP_RESULT_LEN]: T (16), fitness, inlier_rmse, n_corr, iterations (updates made),
- * converged (1 when the stop test ended the loop), 3 unused.  corr_out is DEVICE int32 [n_source]
+ * converged (1 when the stop test ended the loop), 3 unused (written as 0).  corr_out is DEVICE int32 [n_source]
  * or NULL: the last evaluation's correspondences.  log_out is DEVICE float64
  * [max_iteration + 1][SLG_ICP_LOG_STRIDE] or NULL, one record per evaluation (iterations + 1 are
  * written): the T it was made at (16), n_corr, err2, fitness, rmse, the 21 + 6 sums, the x of the

@@ -383,7 +383,7 @@ def voxel_down_sample(pc, voxel_size: float, return_index: bool = False, stream=
     obgr = torch.empty((n, 3), dtype=torch.uint8, device=dev)
     first = torch.empty(n, dtype=torch.int64, device=dev)
     count = torch.empty(n, dtype=torch.int32, device=dev)
-    m = torch.zeros(1, dtype=torch.int64, device=dev)
+    m = torch.empty(1, dtype=torch.int64, device=dev)           # written by the call (as every output here)
     _call(N.lib().slg_voxel_downsample, dev, _filter_ws(xyz, 0), (xyz, pc.bgr, n, float(voxel_size)),
           (oxyz, obgr, first, count, m), stream, "voxel_down_sample")
     m = int(m.item())
@@ -526,7 +526,7 @@ def _register(what, source, target, max_correspondence_distance, init, relative_
     nrm = target.normals.contiguous() if target.has_normals() else None
     ns, nt = src.shape[0], tgt.shape[0]
     L = N.lib()
-    out = torch.zeros(N.ICP_RESULT_LEN + (it + 1) * N.ICP_LOG_STRIDE, dtype=torch.float64, device=dev)
+    out = torch.empty(N.ICP_RESULT_LEN + (it + 1) * N.ICP_LOG_STRIDE, dtype=torch.float64, device=dev)
     corr = torch.empty(ns, dtype=torch.int32, device=dev)
     _call(L.slg_icp_point_to_plane, dev, lambda: L.slg_icp_ws_bytes(ns, nt, it),
           (src, ns, tgt, nrm, nt, d, _dbl16(T0), rf, rr, it), (out, corr, out[N.ICP_RESULT_LEN:]), stream, what)
@@ -644,7 +644,7 @@ def feature_nearest(source_feature: torch.Tensor, target_feature: torch.Tensor, 
     pairs = torch.empty((ns, 2), dtype=torch.int64, device=dev)
     nn_s = torch.empty(ns, dtype=torch.int32, device=dev)
     nn_t = torch.empty(nt, dtype=torch.int32, device=dev) if mutual_filter else None
-    m = torch.zeros(1, dtype=torch.int64, device=dev)
+    m = torch.empty(1, dtype=torch.int64, device=dev)
     L = N.lib()
     _call(L.slg_feature_match, dev, lambda: L.slg_feature_match_ws_bytes(ns, nt),
           (a, ns, b, nt, int(bool(mutual_filter))), (nn_s, nn_t, pairs, m), stream)
@@ -719,7 +719,7 @@ def ransac_batch(source, target, pairs: torch.Tensor, max_correspondence_distanc
     if prepare:
         _call(L.slg_ransac_prepare, dev, need, (tgt, nt), (), stream)
     records = torch.empty((count, N.RANSAC_RECORD_STRIDE), dtype=torch.float64, device=dev)
-    n_eval = torch.zeros(2, dtype=torch.int32, device=dev)
+    n_eval = torch.empty(2, dtype=torch.int32, device=dev)
     trials = torch.empty((count, N.RANSAC_TRIAL_STRIDE), dtype=torch.float64, device=dev) if return_trials else None
     corr = torch.empty((int(corr_cap), ns), dtype=torch.int32, device=dev) if corr_cap else None
     ws = _call(L.slg_ransac_batch, dev, need,
@@ -892,8 +892,8 @@ def plane_finish(pc, plane, distance_threshold, stream=None):
     pl = np.ascontiguousarray(np.asarray(plane, np.float64).reshape(4))
     L = N.lib()
     index = torch.empty(n, dtype=torch.int64, device=dev)
-    count = torch.zeros(1, dtype=torch.int64, device=dev)
-    out = torch.zeros(N.PLANE_SUMS_LEN + 4, dtype=torch.float64, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    out = torch.empty(N.PLANE_SUMS_LEN + 4, dtype=torch.float64, device=dev)
     ws = _call(L.slg_plane_finish, dev, lambda: L.slg_plane_ws_bytes(n, PLANE_BATCH),
                (xyz, n, _dbl16(pl), float(distance_threshold)), (index, count, out, out[N.PLANE_SUMS_LEN:]), stream)
     host = out.cpu().numpy()
@@ -1029,7 +1029,7 @@ def euclidean_mst(pc, return_stats: bool = False, list_k: int = EMST_LIST_K, str
     xyz = _check_xyz(pc.xyz)
     n, dev = xyz.shape[0], xyz.device
     buf = torch.empty((max(n - 1, 1), 2), dtype=torch.int64, device=dev)     # never a NULL buffer
-    stats = torch.zeros(N.ORIENT_STATS_LEN, dtype=torch.int32, device=dev)
+    stats = torch.empty(N.ORIENT_STATS_LEN, dtype=torch.int32, device=dev)
     L = N.lib()
     _call(L.slg_emst, dev, lambda: L.slg_orient_ws_bytes(n, k), (xyz, n, k), (buf, stats), stream, "euclidean_mst")
     edges = _sorted_edges(buf[:n - 1])
@@ -1053,8 +1053,8 @@ def orient_normals_consistent_tangent_plane(pc, k: int, return_tree: bool = Fals
     out = torch.empty_like(nrm)
     emst = torch.empty((n - 1, 2), dtype=torch.int64, device=dev)            # optional outputs: a single point has none
     tree = torch.empty((n - 1, 2), dtype=torch.int64, device=dev)
-    root = torch.zeros(1, dtype=torch.int64, device=dev)
-    stats = torch.zeros(N.ORIENT_STATS_LEN, dtype=torch.int32, device=dev)
+    root = torch.empty(1, dtype=torch.int64, device=dev)
+    stats = torch.empty(N.ORIENT_STATS_LEN, dtype=torch.int32, device=dev)
     L = N.lib()
     _call(L.slg_orient_tangent, dev, lambda: L.slg_orient_ws_bytes(n, k), (xyz, nrm, n, k),
           (out, emst, tree, root, stats), stream, "orient_normals_consistent_tangent_plane")

@@ -292,6 +292,9 @@ void icp_solve_kernel(Hdr* hdr, IcpState* st, const double* __restrict__ part, i
   result[18] = n_corr;
   result[19] = (double)step;
   result[20] = stop ? 1.0 : 0.0;
+  result[21] = 0.0;                          // reserved: written, so result_out needs no clearing by the caller
+  result[22] = 0.0;
+  result[23] = 0.0;
   double x[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   int flags = (stop ? SLG_ICP_LOG_STOP : 0) | (last && !stop ? SLG_ICP_LOG_LAST : 0);
   if (last) {

@@ -678,12 +678,12 @@ void stl_pack_kernel(const double* __restrict__ vert, const int32_t* __restrict_
 static int nodes_grid(int64_t n1) { return (int)((cube(n1) + 255) / 256); }
 
 // One V(2,2) cycle from level l down and back.
-static void vcycle(const MeshHdr* hdr, const SolveWs& w, int l, int R, hipStream_t st) {
+static int vcycle(const MeshHdr* hdr, const SolveWs& w, int l, int R, hipStream_t st) {
   const int r = R >> l;
   const uint32_t n1 = r + 1;
   const double mul = (double)(1 << l);
   const Level& L = w.lv[l];
-  if (r == 2) { coarsest_kernel<<<1, 64, 0, st>>>(hdr, L.u, L.f, mul); return; }
+  if (r == 2) { coarsest_kernel<<<1, 64, 0, st>>>(hdr, L.u, L.f, mul); return SLG_OK; }
   const int g = nodes_grid(n1);
   smooth_kernel<<<g, 256, 0, st>>>(hdr, L.u, L.f, L.tmp, n1, mul);
   smooth_kernel<<<g, 256, 0, st>>>(hdr, L.tmp, L.f, L.u, n1, mul);
@@ -691,11 +691,13 @@ static void vcycle(const MeshHdr* hdr, const SolveWs& w, int l, int R, hipStream
   const Level& C = w.lv[l + 1];
   const uint32_t n1c = r / 2 + 1;
   restrict_kernel<<<nodes_grid(n1c), 256, 0, st>>>(hdr, L.tmp, C.f, n1c);
-  (void)hipMemsetAsync(C.u, 0, cube(n1c) * sizeof(double), st);
-  vcycle(hdr, w, l + 1, R, st);
+  if (hipMemsetAsync(C.u, 0, cube(n1c) * sizeof(double), st) != hipSuccess)
+    return slg_internal_fail(SLG_ERR_HIP, "slg_mesh_solve: memset failed");
+  if (int rc = vcycle(hdr, w, l + 1, R, st)) return rc;
   prolong_kernel<<<g, 256, 0, st>>>(hdr, L.u, C.u, n1);
   smooth_kernel<<<g, 256, 0, st>>>(hdr, L.u, L.f, L.tmp, n1, mul);
   smooth_kernel<<<g, 256, 0, st>>>(hdr, L.tmp, L.f, L.u, n1, mul);
+  return SLG_OK;
 }
 
 static size_t stage_bytes(int stage, int R, int64_t n, int64_t m) {
@@ -804,7 +806,8 @@ extern "C" int32_t slg_mesh_solve(const double* f, int32_t R, int32_t cycles, vo
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(chi_out, 0, cube(R + 1) * sizeof(double), st) != hipSuccess)
     return slg_internal_fail(SLG_ERR_HIP, "slg_mesh_solve: memset failed");
-  for (int c = 0; c < cycles; ++c) vcycle((const MeshHdr*)ws, w, 0, R, st);
+  for (int c = 0; c < cycles; ++c)
+    if (int rc = vcycle((const MeshHdr*)ws, w, 0, R, st)) return rc;
   return check_launch("slg_mesh_solve");
 }
 

@@ -186,7 +186,7 @@ class DeviceCalib:
                 rays = torch.from_numpy(Nc.T).to(device).t().contiguous()
             else:
                 rays = torch.from_numpy(np.ascontiguousarray(Nc, dtype=np.float64)).to(device)
-            mism = torch.zeros(1, dtype=torch.int64, device=device)
+            mism = torch.empty(1, dtype=torch.int64, device=device)      # cleared by the call on its stream
             N.check(N.lib().slg_rays_match_pinhole(_vp(rays), self.height, self.width, self.fx,
                                                    self.fy, self.cx, self.cy, _vp(mism), _stream()))
             self.table_is_pinhole = int(mism.item()) == 0

@@ -5,13 +5,13 @@
 * C2 bench shape: ``BatchReconstructor.run_pipelined(mode="fused")`` over 36 full-size 1920x1080
   views, 12 per main3 launch, 2 workspace slots, batch k carrying batch k+2's Otsu histograms
   (per-tile partials -> parts_kernel), issued in two pieces (the stream continuation bench.py
-  uses).  Every view's count equals the oracle's; f32 clouds within the north-star tolerance
+  uses).  Every view's count equals the oracle's; f32 clouds the oracle's rounded once to float32
   and f64 clouds bit-exact on a subset; the 1013-tile look-back chains are full length.
 * C3: the 36-view turntable job at 1080p with 11 + 11 bits through the sharded path's pieces
   (12-view batches, the C-ABI RCCL gatherv at world size 1): every view's count and a subset of
   clouds (f64, bit for bit) against the oracle, gathered layout checked.
 * C5 geometry: a 3840x2160 view, projector 1920x1080, 11 + 11 bits, row_mode 1 -- maps, f64
-  cloud bit-exact, f32 within tolerance, codes equal the renderer's ground truth; and a 2-view
+  cloud bit-exact, f32 the same rounded once, codes equal the renderer's ground truth; and a 2-view
   batch of them.
 """
 from concurrent.futures import ThreadPoolExecutor
@@ -20,17 +20,11 @@ import numpy as np
 import pytest
 
 from oracle import sl_oracle as O
+from xyz32 import assert_xyz32_exact
 
 pytestmark = pytest.mark.gpu
 
-XYZ32_RTOL = 1e-4     # BASELINE.json north_star: XYZ within 1e-4 relative (fp32 vs float64)
 N_VIEWS = 36
-
-
-def _xyz32_close(got, want):
-    got = np.asarray(got, np.float64)
-    scale = np.maximum(np.abs(want), 1e-3)
-    assert np.all(np.abs(got - want) <= XYZ32_RTOL * scale)
 
 
 @pytest.fixture(scope="module")
@@ -63,7 +57,7 @@ def _oracle_all(cal, views, nsets, row_mode=1):
 
 def test_c2_bench_launch_shape(mods, scan):
     """The benchmark's exact shape: 12 C2 views per fused launch, two slots, carried histograms;
-    every view's count, colours and XYZ (f64 bit for bit, f32 within the north-star tolerance)."""
+    every view's count, colours and XYZ (f64 bit for bit, f32 the oracle rounded once to float32)."""
     E, N = mods
     import torch
     cal, views = scan
@@ -88,7 +82,7 @@ def test_c2_bench_launch_shape(mods, scan):
             if f64:
                 assert np.array_equal(P, Po), k
             else:
-                _xyz32_close(P, Po)
+                assert_xyz32_exact(P, Po)
         assert all(eng.header(s, v)[3084:3088].cpu().numpy()[0] & 1 == 0 for s in range(2) for v in range(12))
     assert min(len(w[0]) for w in want) > 500_000
 
@@ -123,7 +117,7 @@ def test_c2_two_stream_pipeline(mods, scan, bv):
         P, C = c.result()
         assert P.shape[0] == Po.shape[0], (k, P.shape[0], Po.shape[0])
         assert np.array_equal(C.cpu().numpy(), Co), k
-        _xyz32_close(P.cpu().numpy(), Po)
+        assert_xyz32_exact(P.cpu().numpy(), Po)
     assert all(eng.header(s, v)[3084:3088].cpu().numpy()[0] & 1 == 0 for s in range(4) for v in range(bv))
 
 
@@ -192,7 +186,7 @@ def test_c5_full_size(mods):
     assert np.array_equal(P.cpu().numpy(), Po) and np.array_equal(C.cpu().numpy(), Co)
     P, C = eng.reconstruct(dev[0], cfg, dcal, 1, xyz_f64=False).result()
     assert len(P) == len(Po) and np.array_equal(C.cpu().numpy(), Co)
-    _xyz32_close(P.cpu().numpy(), Po)
+    assert_xyz32_exact(P.cpu().numpy(), Po)
     assert eng.error_flags() & 1 == 0
     # the 2-view batch of the bench's c5 shape (stats + one fused launch, f32)
     beng = E.BatchReconstructor(2160, 3840, 2)
@@ -203,7 +197,7 @@ def test_c5_full_size(mods):
     for o, (Pw, Cw) in zip(outs, [(Po, Co), (Po2, Co2)]):
         P, C = o.result()
         assert len(P) == len(Pw) and np.array_equal(C.cpu().numpy(), Cw)
-        _xyz32_close(P.cpu().numpy(), Pw)
+        assert_xyz32_exact(P.cpu().numpy(), Pw)
 
 
 def test_c5_resident_job(mods):
@@ -211,7 +205,7 @@ def test_c5_resident_job(mods):
     jobs.ResidentJob): 3840x2160 views, each an HBM copy of one of 2 captures per object, one
     fused launch per view on the two-stream carried pipeline (4 primed + 4 carried groups), the
     clouds packed in one arena by capacity hints.  Every view's count and colours equal the
-    oracle's, XYZ within the north-star tolerance; a view given too small a hint is reported as
+    oracle's, XYZ (f32) the oracle's rounded once; a view given too small a hint is reported as
     overflowed and its successor as damaged (the stores stay inside the arena); the default
     device-reserved arena (no sizing pass), one too small for the job, and row_mode 2."""
     E, N = mods
@@ -243,7 +237,7 @@ def test_c5_resident_job(mods):
     for j, p in enumerate(plan):
         x, b = job.cloud(j, counts)
         assert np.array_equal(b.cpu().numpy(), want[p][1]), j
-        _xyz32_close(x.cpu().numpy(), want[p][0])
+        assert_xyz32_exact(x.cpu().numpy(), want[p][0])
     small = list(hints)
     small[2] -= 1000                                    # view 2 cannot fit: flagged, not faulted
     job2 = J.ResidentJob(views[:4], cfg, dcal, batch=2, capacity_hints=small[:4])
@@ -260,7 +254,7 @@ def test_c5_resident_job(mods):
     for j in range(4):
         x, b = job2.cloud(j)
         assert np.array_equal(b.cpu().numpy(), want[plan[j]][1]), j
-        _xyz32_close(x.cpu().numpy(), want[plan[j]][0])
+        assert_xyz32_exact(x.cpu().numpy(), want[plan[j]][0])
     # the default: a device-reserved arena -- each view's region reserved by the kernel that
     # finishes its thresholds, min(#white >= smin, #(white - black) >= cmin) points (an upper
     # bound of its count), no sizing pass, nothing can overflow
@@ -276,7 +270,7 @@ def test_c5_resident_job(mods):
     for j, p in enumerate(plan):
         x, b = job3.cloud(j, counts3)
         assert np.array_equal(b.cpu().numpy(), want[p][1]), j
-        _xyz32_close(x.cpu().numpy(), want[p][0])
+        assert_xyz32_exact(x.cpu().numpy(), want[p][0])
     # an arena with room for about two views: the others are refused (they store nothing), named
     # by overflowed(), refused by cloud() and recovered by recover()
     job4 = J.ResidentJob(views[:4], cfg, dcal, batch=2, arena_points=2 * max(hints) + 1000)
@@ -291,7 +285,7 @@ def test_c5_resident_job(mods):
     for j in range(4):
         x, b = job4.cloud(j)
         assert np.array_equal(b.cpu().numpy(), want[plan[j]][1]), j
-        _xyz32_close(x.cpu().numpy(), want[plan[j]][0])
+        assert_xyz32_exact(x.cpu().numpy(), want[plan[j]][0])
     # row_mode 2 (server/processing.py:209-234: column cloud then row cloud): reserved at twice
     # the bound, every view equal to the oracle's concatenated clouds, f64 bit for bit
     want2 = _oracle_all(cal, caps, (11, 11), row_mode=2)

@@ -8,15 +8,16 @@ small synthetic view (a ragged 320x200 camera: the tail tile's guarded path) who
 parameters select one instance.  Its row planes are shifted so that row_mode 1 rejects about two
 points in three.  ``slg_last_kernel`` names the instance each launch picked, so
 the test checks which instance produced each cloud.  f64 clouds must equal the oracle
-(``server/processing.py:127-234`` restated) bit for bit; f32 ones must be within XYZ32_RTOL,
-with colours and point order exact.
+(``server/processing.py:127-234`` restated) bit for bit; f32 ones must equal the
+oracle's cloud rounded once to float32, bit for bit (tests/xyz32.py), with colours and point order
+exact.
 """
 import numpy as np
 import pytest
 
 from oracle import sl_oracle as O
+from xyz32 import assert_xyz32_exact
 
-XYZ32_RTOL = 1e-4     # BASELINE.json north_star: XYZ within 1e-4 relative (fp32 vs float64)
 CAM = (320, 200)
 GRAY_BIT = 0x100      # csrc/slgpu.hip kPlanGray
 
@@ -122,8 +123,7 @@ def test_every_fused_instance_matches_oracle(case):
     if x64:
         assert np.array_equal(P, Po), f"max |d| {np.abs(P - Po).max()}"
     else:
-        scale = np.maximum(np.abs(Po), 1e-3)
-        assert np.all(np.abs(P.astype(np.float64) - Po) <= XYZ32_RTOL * scale)
+        assert_xyz32_exact(P, Po, case[0])
     assert eng.error_flags() & 1 == 0
 
 

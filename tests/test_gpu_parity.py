@@ -1,6 +1,7 @@
 """GPU parity: the HIP path (through the C ABI) against the reference's golden vectors and the
 oracle.  Integer/byte outputs (maps, mask, colours, order, counts) must be bit-exact; XYZ
-must be bit-exact in the float64 mode and within 1e-4 relative (north star) in float32 mode.
+must be bit-exact in the float64 mode, and in float32 mode equal to the float64 reference rounded
+once to float32, bit for bit (tests/xyz32.py; the north star's 1e-4 relative follows from it).
 """
 import os
 
@@ -9,10 +10,9 @@ import pytest
 
 from conftest import decode_kwargs, expected_cloud, golden_cases, load_calibs, load_case
 from oracle import sl_oracle as O
+from xyz32 import assert_xyz32_exact
 
 pytestmark = pytest.mark.gpu
-
-XYZ32_RTOL = 1e-4     # BASELINE.json north_star: XYZ within 1e-4 relative (fp32 vs float64)
 
 
 @pytest.fixture(scope="module")
@@ -32,12 +32,6 @@ def _cfg(E, p):
     return E.DecodeConfig(kw.get("n_cols", 1920), kw.get("n_rows", 1080), kw.get("n_sets_col", 11),
                           kw.get("n_sets_row", 11), kw.get("thresh_mode", "otsu"),
                           kw.get("shadow_val", 40), kw.get("contrast_val", 10))
-
-
-def _xyz32_close(got, want):
-    got = np.asarray(got, np.float64)
-    scale = np.maximum(np.abs(want), 1e-3)
-    assert np.all(np.abs(got - want) <= XYZ32_RTOL * scale)
 
 
 @pytest.mark.parametrize("name", golden_cases())
@@ -103,9 +97,10 @@ def test_cloud_f32_within_tolerance(name, mods):
             continue
         P, C = eng.reconstruct(dev, _cfg(E, z["params"]), dc, row_mode=rm, xyz_f64=False).result()
         assert P.dtype.itemsize == 4
-        assert len(P) == len(z[f"P{rm}"])
-        _xyz32_close(P.cpu().numpy(), z[f"P{rm}"])
-        assert np.array_equal(C.cpu().numpy(), z[f"C{rm}"])
+        Pw, Cw = expected_cloud(z, cal, rm)
+        assert len(P) == len(Pw)
+        assert_xyz32_exact(P.cpu().numpy(), Pw, f"{name} row_mode {rm}")
+        assert np.array_equal(C.cpu().numpy(), Cw)
 
 
 @pytest.mark.parametrize("name", ["proc_c2style", "proc_odd_geometry", "proc_manual_sets"])
@@ -290,7 +285,7 @@ def test_full_size_parity(cam, proj, nsets, thresh, mods):
 def test_full_size_row_modes(rm, mods):
     """C2 geometry at full size in row_mode 0 and 2 (the col + row clouds; row planes nearly
     parallel to the rays, the ill-conditioned case): the fused path and the maps-in
-    triangulation both equal the oracle bit for bit in f64, and within XYZ32_RTOL in f32."""
+    triangulation both equal the oracle bit for bit in f64, and the oracle rounded once to float32 in f32."""
     E, PR, N = mods
     import torch
     from structured_light_for_3d_model_replication_amd import synth
@@ -312,13 +307,13 @@ def test_full_size_row_modes(rm, mods):
     assert np.array_equal(P.cpu().numpy(), Po) and np.array_equal(C.cpu().numpy(), Co)
     P, C = eng.reconstruct(dev, cfg, dc, rm, xyz_f64=False).result()
     assert len(P) == len(Po) and np.array_equal(C.cpu().numpy(), Co)
-    _xyz32_close(P.cpu().numpy(), Po)
+    assert_xyz32_exact(P.cpu().numpy(), Po)
 
 
 def test_c4_full_size_parity(mods):
     """BASELINE configs[3] (C4): 6000x4000 capture, projector 3840x2160 (12 + 12 bits, 50
     frames), Otsu, row_mode 1.  Maps and the f64 cloud equal the oracle bit for bit, the f32
-    cloud is within XYZ32_RTOL, and the decoded codes equal the renderer's ground truth on lit,
+    cloud is the oracle's rounded once to float32, and the decoded codes equal the renderer's ground truth on lit,
     valid pixels (size-independent property)."""
     E, PR, N = mods
     from structured_light_for_3d_model_replication_amd import synth
@@ -344,7 +339,7 @@ def test_c4_full_size_parity(mods):
     assert np.array_equal(P.cpu().numpy(), Po) and np.array_equal(C.cpu().numpy(), Co)
     P, C = eng.reconstruct(dev, cfg, dc, 1, xyz_f64=False).result()
     assert len(P) == len(Po) and np.array_equal(C.cpu().numpy(), Co)
-    _xyz32_close(P.cpu().numpy(), Po)
+    assert_xyz32_exact(P.cpu().numpy(), Po)
     assert eng.error_flags() & 1 == 0
 
 
