@@ -199,7 +199,21 @@ EXPORTS = {
     "slg_mesh_decimate_round": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp]),
     "slg_mesh_decimate_emit": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
 }
-MESH_HDR_BYTES, MESH_MAX_DEPTH = 256, 10         # SLG_MESH_HDR_BYTES; kMaxDepth of csrc/cloud_mesh.hip
+# The surface mesher's table (include/slgpu_surface.h, csrc/cloud_surface.hip): the same library,
+# bound by the same lib().  A table of its own until a change that may edit the tests pinned to
+# EXPORTS folds the two together.
+SURFACE_EXPORTS = {
+    "slg_surface_ws_bytes": (c_i64, [c_i32, c_i64, c_i64, c_i64]),
+    "slg_surface_begin": (c_i32, [c_vp, c_i64, c_dbl, c_vp, c_i64, c_vp]),
+    "slg_surface_count": (c_i32, [c_vp, c_vp, c_i64, c_dbl, c_vp, c_i64, c_vp, c_vp]),
+    "slg_surface_emit": (c_i32, [c_vp, c_vp, c_i64, c_dbl, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp]),
+    "slg_surface_round": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp]),
+    "slg_surface_commit": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
+}
+SURFACE_WS_GRID, SURFACE_WS_PASS = 0, 1          # SLG_SURFACE_WS_*
+SURFACE_MAX_NEIGHBOURS, SURFACE_MAX_RADII = 512, 8   # SLG_SURFACE_MAX_NEIGHBOURS, SLG_SURFACE_MAX_RADII
+FILTER_BAD_NEIGHBOURS = 8                        # SLG_FILTER_BAD_NEIGHBOURS (slgpu_surface.h)
+MESH_HDR_BYTES, MESH_MAX_DEPTH = 256, 10        # SLG_MESH_HDR_BYTES; kMaxDepth of csrc/cloud_mesh.hip
 # SLG_MESH_WS_*: the stages of slg_mesh_ws_bytes
 (MESH_WS_GRID, MESH_WS_SPLAT, MESH_WS_SOLVE, MESH_WS_ISO, MESH_WS_EXTRACT, MESH_WS_QUANTILE, MESH_WS_REMOVE,
  MESH_WS_ALL) = range(8)
@@ -261,6 +275,14 @@ def _load():
         fn = getattr(h, name)
         fn.restype = res
         fn.argtypes = args
+    # The second table: the digest check below vouches that the product library is the build of
+    # sources that hold it (tests/test_surface_host.py looks every name up).  A handle without a
+    # name gets no prototype, and the first call of that name raises ctypes' AttributeError.
+    for name, (res, args) in SURFACE_EXPORTS.items():
+        if hasattr(h, name):
+            fn = getattr(h, name)
+            fn.restype = res
+            fn.argtypes = args
     if h.slg_version() != ABI_VERSION:
         raise ImportError("libslgpu ABI version mismatch")
     if AB_LIB is None:

@@ -15,6 +15,11 @@ DESIGN.md §17): :func:`vertex_adjacency`, :func:`smooth_laplacian`, :func:`smoo
 :func:`close_holes`, :func:`boundary_loops` and :func:`postprocess`, restated in
 ``tests/meshpost_ref.py``, and :func:`decimate_quadric` (``csrc/cloud_decimate.hip``),
 restated in ``tests/decimate_ref.py``; parity with MeshLab / VCGlib is unpinned.
+
+Beside the watertight mesher, the surface mesh of ``reconstruct_stl(mode="surface")`` under the
+device's own rule (``csrc/cloud_surface.hip``): :func:`ball_pivot`, the empty-ball
+triangles radius by radius, restated in ``tests/surface_ref.py``; parity with Open3D's ball
+pivoting is unpinned.
 """
 from __future__ import annotations
 
@@ -661,6 +666,135 @@ def decimate_quadric(mesh: TriangleMesh, target_faces, max_rounds: int = 512, re
                                              E._vp(t_out), alive, st))
     out = TriangleMesh(v_out, t_out, d_out)
     return (out, rec) if return_record else out
+
+
+# ----------------------------------------------------------------------------- surface meshing
+# The empty-ball triangles of an oriented cloud, radius by radius (csrc/cloud_surface.hip): our
+# rule, restated in tests/surface_ref.py and equal to it bit for bit; parity with Open3D's ball
+# pivoting is unpinned.
+MAX_RADII, MAX_SURFACE_NEIGHBOURS = N.SURFACE_MAX_RADII, N.SURFACE_MAX_NEIGHBOURS
+DEFAULT_SURFACE_ROUNDS = 64
+_PASS_HDR = np.dtype([("status", "<i4"), ("pad", "<i4"), ("live", "<i8"), ("accepted", "<i8"), ("cursor", "<u8")])
+
+
+def check_radii(radii, what: str = "ball_pivot") -> list:
+    """``radii`` as a list of floats when they are 1 to 8 finite, positive, strictly ascending
+    numbers, else ``ValueError``."""
+    try:
+        rs = [float(r) for r in np.asarray(radii, dtype=np.float64).reshape(-1)]
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: radii must be numbers, not {radii!r}") from None
+    if not 1 <= len(rs) <= MAX_RADII:
+        raise ValueError(f"{what}: between 1 and {MAX_RADII} radii, not {len(rs)}")
+    if not all(np.isfinite(r) and r > 0.0 for r in rs):
+        raise ValueError(f"{what}: radii must be finite and > 0, not {rs}")
+    if any(b <= a for a, b in zip(rs, rs[1:])):
+        raise ValueError(f"{what}: radii must be strictly ascending, not {rs}")
+    return rs
+
+
+def ball_pivot(pc, radii, max_rounds: int = DEFAULT_SURFACE_ROUNDS, return_record: bool = False, stream=None, timings=None):
+    """The surface mesh of an oriented cloud: the triangles on which a ball of radius ``r`` rests,
+    on the normals' side, with no point inside, for ``r`` in ``radii`` in turn (what Open3D's
+    ``create_from_point_cloud_ball_pivoting`` converges to, without its front: our rule,
+    DESIGN.md §20, Open3D parity unpinned).
+
+    State across the passes: the directed edges ``taken`` and a flag ``closed`` per vertex.  A pass
+    takes every triple ``a < b < c`` of vertices that are not closed with squared sides ``< 4 r^2``
+    that is not flat, has a circumradius ``rho <= r``, whose three normals lie on one side of its
+    plane (that side gives the winding) and whose ball holds no other point ``j`` with
+    ``d2(P[j], o) < r^2 (1 - 2^-30)``; ranks them by ``(bits of rho^2, a, b, c)``; and accepts, in
+    rank order, those none of whose directed edges is taken (found in rounds of integer minima,
+    at most ``max_rounds``: reaching that raises ``RuntimeError``).  Then ``closed[v]`` iff ``v`` has a
+    taken edge and every taken edge at ``v`` has its reverse.  No directed edge is used twice, so
+    the mesh is orientable and edge-manifold, and every triangle agrees with its three normals;
+    vertex-manifoldness is not promised.
+
+    A :class:`TriangleMesh`: ``vertices`` is the cloud's ``xyz`` (all points, as Open3D keeps them),
+    ``triangles`` int32 ``[T, 3]``, the passes in order and within a pass in ascending rank.  With
+    ``return_record`` also a list with one dict per radius (``radius``, ``candidates``,
+    ``accepted``, ``rounds``).  Fewer than 3 points give an empty mesh without a device call.
+    ``ValueError`` for a cloud without normals, bad ``radii`` (:func:`check_radii`), a non-finite
+    coordinate, 2^21 or more cells of ``2 r`` on an axis, or a point with more than
+    ``MAX_SURFACE_NEIGHBOURS`` open neighbours of higher index within ``2 r`` (the message names
+    the radius).  ``timings``: a list that gets one dict per pass with the stages' times in ms by
+    HIP events (``grid``, ``count``, ``emit``, ``select``: the rounds with their read-backs,
+    ``commit``) beside the record's entries."""
+    rs = check_radii(radii)
+    if isinstance(max_rounds, float) and not max_rounds.is_integer() or int(max_rounds) < 1:
+        raise ValueError(f"ball_pivot: max_rounds must be a whole number >= 1, not {max_rounds}")
+    max_rounds = int(max_rounds)
+    pc = CL.as_point_cloud(pc)
+    if pc.normals is None:
+        raise ValueError("ball_pivot: the cloud has no normals (estimate and orient them first)")
+    n = len(pc)
+    record = [dict(radius=r, candidates=0, accepted=0, rounds=0) for r in rs]
+    if n < 3:
+        out = TriangleMesh(pc.xyz, torch.zeros((0, 3), dtype=torch.int32, device=pc.xyz.device))
+        return (out, record) if return_record else out
+    xyz, nrm = CL._check_xyz(pc.xyz), pc.normals.contiguous()
+    if nrm.dtype != torch.float64 or nrm.shape != xyz.shape or nrm.device != xyz.device:
+        raise ValueError("ball_pivot: normals must be a float64 [n, 3] tensor beside the points")
+    dev, lib, st = xyz.device, N.lib(), E._stream(stream)
+    parts = []
+    with torch.cuda.device(dev):
+        gws = CL._workspace(dev, lib.slg_surface_ws_bytes(N.SURFACE_WS_GRID, n, 0, 0))
+        closed = torch.zeros(n, dtype=torch.uint8, device=dev)
+        taken, n_taken = torch.empty(1, dtype=torch.int64, device=dev), 0
+        total = torch.empty(1, dtype=torch.int64, device=dev)
+        for rec in record:
+            r = rec["radius"]
+            marks = _Stages({} if timings is not None else None, stream)
+            marks.mark("start")
+            CL._raise(lib.slg_surface_begin(E._vp(xyz), n, r, E._vp(gws), gws.numel(), st))
+            marks.mark("grid")
+            CL._raise(lib.slg_surface_count(E._vp(nrm), E._vp(closed), n, r, E._vp(gws), gws.numel(), E._vp(total), st))
+            status = int(gws[:4].view(torch.int32).item())          # synchronises the stream
+            if status & N.FILTER_BAD_NONFINITE:
+                raise ValueError("ball_pivot: the cloud holds a NaN or infinite coordinate")
+            if status & N.FILTER_BAD_EXTENT:
+                raise ValueError(f"ball_pivot: the cloud spans 2^21 or more cells of twice the radius {r!r} on an axis")
+            if status & N.FILTER_BAD_NEIGHBOURS:
+                raise ValueError(f"ball_pivot: at radius {r!r} a point has more than {MAX_SURFACE_NEIGHBOURS} open neighbours "
+                                 "of higher index within twice the radius (the list is never cut short)")
+            nc = int(total.item())
+            marks.mark("count")
+            if 3 * nc > 1 << 30:
+                raise ValueError(f"ball_pivot: {nc} candidate triangles at radius {r!r}: more than 2^30 directed edges")
+            rec["candidates"] = nc
+            if nc:
+                need = int(lib.slg_surface_ws_bytes(N.SURFACE_WS_PASS, n, nc, n_taken))
+                if need < 0:
+                    CL._raise(-need)
+                pws = torch.empty(need, dtype=torch.uint8, device=dev)
+                CL._raise(lib.slg_surface_emit(E._vp(nrm), E._vp(closed), n, r, E._vp(gws), gws.numel(), E._vp(taken), n_taken,
+                                               E._vp(pws), pws.numel(), nc, st))
+                marks.mark("emit")
+                while True:
+                    if rec["rounds"] >= max_rounds:
+                        raise RuntimeError(f"ball_pivot: the selection at radius {r!r} did not end in {max_rounds} rounds")
+                    CL._raise(lib.slg_surface_round(E._vp(pws), pws.numel(), n, nc, n_taken, st))
+                    hdr = np.frombuffer(pws[:_PASS_HDR.itemsize].cpu().numpy().tobytes(), dtype=_PASS_HDR)[0]
+                    rec["rounds"] += 1                 # the one read-back per round: whether there is another
+                    if int(hdr["live"]) == 0:
+                        break
+                marks.mark("select")
+                na = rec["accepted"] = int(hdr["accepted"])
+                if na:
+                    tris = torch.empty((na, 3), dtype=torch.int32, device=dev)
+                    merged = torch.empty(n_taken + 3 * na, dtype=torch.int64, device=dev)
+                    CL._raise(lib.slg_surface_commit(E._vp(pws), pws.numel(), n, nc, E._vp(taken), n_taken, na, E._vp(tris),
+                                                     E._vp(merged), E._vp(closed), st))
+                    parts.append(tris)
+                    taken, n_taken = merged, n_taken + 3 * na
+                marks.mark("commit")
+            marks.close()
+            if timings is not None:
+                timings.append(dict(radius=r, candidates=nc, accepted=rec["accepted"], rounds=rec["rounds"],
+                                    **{k[:-3]: v for k, v in marks.timings.items()}))
+        triangles = torch.cat(parts) if parts else torch.zeros((0, 3), dtype=torch.int32, device=dev)
+    out = TriangleMesh(xyz, triangles)
+    return (out, record) if return_record else out
 
 
 def check_postprocess(params) -> None:

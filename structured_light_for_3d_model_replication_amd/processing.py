@@ -687,6 +687,18 @@ class ProcessingLogic:
         return MS.check_depth(depth)
 
     @staticmethod
+    def _surface_multipliers(radii_str):
+        """``params["radii"]`` parsed as the reference does (``server/processing.py:720``), and what
+        ``mesh.check_radii`` will ask of their multiples of a positive distance, asked here."""
+        from . import mesh as MS
+        try:
+            multipliers = [float(x) for x in radii_str.split(',')]
+            MS.check_radii(sorted(set(multipliers)), "reconstruct_stl")
+        except Exception as e:
+            raise ValueError(f"Invalid radii parameters: {e}")
+        return multipliers
+
+    @staticmethod
     def _write_mesh(mesh, output_path, tag):
         from . import mesh as MS
         MS.compute_triangle_normals(mesh)
@@ -701,7 +713,14 @@ class ProcessingLogic:
         pass, then ``mesh.poisson_grid`` at ``params["depth"]`` (default 10), the 0.02 density
         quantile trim and a binary STL.  The mesher is the dense grid's, so a depth
         above 10 raises ``ValueError``; ``mode="surface"`` (ball pivoting) raises
-        ``NotImplementedError``: it stays in the reference.  The MeshLab step is restated literally
+        ``NotImplementedError``: Open3D's front stays in the reference.  With
+        ``params["surface_rule"] == "empty_ball"`` it runs ``mesh.ball_pivot`` instead (DESIGN.md
+        §20: the empty-ball triangles, our rule and not Open3D's front) at the radii
+        ``np.mean(nearest_neighbor_distance) * m`` for the multipliers ``m`` of ``params["radii"]``
+        (default ``"1,2,4"``), sorted ascending without duplicates; what goes wrong there is a
+        ``ValueError("Invalid radii parameters: ...")`` as in the reference, a mesh without a
+        triangle ``ValueError("Generated mesh is empty.")``, any other rule a ``ValueError``.
+        The MeshLab step is restated literally
         (it needs ``pymeshlab``) unless ``meshlab_params["backend"] == "device"``: then the STL is
         written first as always, ``mesh.postprocess`` (smoothing and hole closing,
         our rules) runs on the float64 mesh in memory and the file is overwritten.  MeshLab would
@@ -720,8 +739,15 @@ class ProcessingLogic:
             depth = ProcessingLogic._check_grid_poisson(params.get("depth", 10))
             MS.check_stl_path(output_path)
         elif mode == "surface":
-            raise NotImplementedError("mode='surface' (ball pivoting) is a sequential front propagation and stays in the "
-                                      "reference (server/processing.py:711-728)")
+            rule = params.get("surface_rule")
+            if rule is None:
+                raise NotImplementedError("mode='surface' (ball pivoting) is a sequential front propagation and stays in the "
+                                          "reference (server/processing.py:711-728); \"surface_rule\": \"empty_ball\" asks for "
+                                          "the device's own rule instead (mesh.ball_pivot)")
+            if rule != "empty_ball":
+                raise ValueError(f"reconstruct_stl: unknown surface_rule {rule!r} (\"empty_ball\": mesh.ball_pivot)")
+            multipliers = ProcessingLogic._surface_multipliers(params.get("radii", "1,2,4"))
+            MS.check_stl_path(output_path)
         else:
             raise ValueError(f"Unknown mode: {mode}")
         backend = meshlab_params.get("backend", "pymeshlab") if meshlab_params and meshlab_params.get("enabled") else None
@@ -753,11 +779,22 @@ class ProcessingLogic:
             print(f"[Recon] Saving normals point cloud to {save_normals_path}...")
             pcd.save(save_normals_path)
             print(f"[Recon] Normals point cloud saved ({len(pcd)} points).")
-        print(f"[Recon] Poisson Reconstruction (depth={depth})...")
-        mesh = MS.poisson_grid(pcd, depth=depth)
-        if len(mesh.vertices):
-            mesh = MS.remove_vertices_by_mask(mesh, mesh.densities < MS.quantile(mesh.densities, 0.02))
-        if len(mesh.vertices) == 0:
+        if mode == "watertight":
+            print(f"[Recon] Poisson Reconstruction (depth={depth})...")
+            mesh = MS.poisson_grid(pcd, depth=depth)
+            if len(mesh.vertices):
+                mesh = MS.remove_vertices_by_mask(mesh, mesh.densities < MS.quantile(mesh.densities, 0.02))
+        else:
+            try:
+                avg_dist = np.mean(CL.nearest_neighbor_distance(pcd).cpu().numpy())
+                radii = sorted({avg_dist * m for m in multipliers})
+                print(f"[Recon] Ball Pivoting (radii={radii})...")
+                mesh = MS.ball_pivot(pcd, radii)
+            except Exception as e:
+                raise ValueError(f"Invalid radii parameters: {e}")
+        # Open3D keeps every point as a vertex, so does ball_pivot: without a triangle the mesh is empty.
+        # mesh.postprocess takes unreferenced vertices as they are (empty adjacency rows).
+        if len(mesh.vertices) == 0 or (mode == "surface" and len(mesh.triangles) == 0):
             raise ValueError("Generated mesh is empty.")
         print("[Recon] Computing normals and saving...")
         ProcessingLogic._write_mesh(mesh, output_path, "Recon")

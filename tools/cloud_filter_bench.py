@@ -83,6 +83,15 @@ outputs), beside its compulsory traffic.  ``--kernel-stats CSV`` takes a ``rocpr
 --stats`` kernel table of a run of this very command and reports the evaluation kernel's time per
 call and its rate against the model.
 
+``--surface RADII`` adds the surface mesher: normals of the view at
+``--surface-normals`` (default radius 1.0 / 30) oriented by the tangent-plane orientation with
+``--surface-orient`` neighbours, then ``mesh.ball_pivot`` at ``RADII`` (multiples of the mean
+nearest-neighbour distance, e.g. ``1,2,4``).  It reports the call's time and per pass the stages'
+times by HIP events (``grid``, ``count``, ``emit``, ``select``, ``commit``) with the candidates, the
+accepted and the rounds.  The CPU side is ``tests/surface_ref.py`` on the view voxel-down-sampled to
+at most ``--surface-cpu-points`` points; the device runs on that cloud too and the tool asserts that
+the triangles and the record are equal.  ``--surface-only`` leaves every other step out.
+
 Prints one JSON line.
 """
 from __future__ import annotations
@@ -136,6 +145,13 @@ def main():
                     help="with --post: also drop every K-th vertex (an open view's trim removes nothing, so this makes the holes)")
     ap.add_argument("--decimate", type=int, metavar="TARGET", help="with --post: also time decimate_quadric to this many faces")
     ap.add_argument("--kernel-stats", metavar="CSV", help="with --decimate: rocprofv3's kernel stats of a run of this command")
+    ap.add_argument("--surface", metavar="RADII", help="also time the surface mesher at these multiples of the mean "
+                                                      "nearest-neighbour distance, e.g. 1,2,4")
+    ap.add_argument("--surface-normals", nargs=2, default=("1.0", "30"), metavar=("RADIUS", "MAX_NN"),
+                    help="with --surface: the normal estimation before it")
+    ap.add_argument("--surface-orient", type=int, default=30, metavar="K", help="with --surface: the tangent-plane orientation's K")
+    ap.add_argument("--surface-cpu-points", type=int, default=20000, help="with --surface: the size the restatement runs at")
+    ap.add_argument("--surface-only", action="store_true", help="with --surface: leave every other step out")
     args = ap.parse_args()
 
     import numpy as np
@@ -168,6 +184,63 @@ def main():
 
     res = {"tool": "cloud_filter_bench", "points": n, "row_mode": args.row_mode, "cam": [W, H],
            "steps": args.steps, "device": torch.cuda.get_device_name(0)}
+    if args.surface:
+        import surface_ref as SR
+        from structured_light_for_3d_model_replication_amd import mesh as MS
+        mult = sorted({float(x) for x in args.surface.split(",")})
+        nr, nk, ok = float(args.surface_normals[0]), int(args.surface_normals[1]), int(args.surface_orient)
+        mean = lambda v: sum(v) / len(v)
+
+        def oriented(cloud, radius):
+            return CL.orient_normals_consistent_tangent_plane(CL.estimate_normals(cloud, radius, nk), ok)
+
+        def radii_of(cloud):
+            avg = float(np.mean(CL.nearest_neighbor_distance(cloud).cpu().numpy()))
+            return avg, [avg * m for m in mult]
+
+        src = oriented(pc, nr)
+        avg, radii = radii_of(src)
+        passes = []
+
+        def run():
+            t = []
+            out = MS.ball_pivot(src, radii, return_record=True, timings=t)
+            passes.append(t)
+            return out
+
+        (mesh, rec), ms = timed(run)
+        print(f"[device] ball_pivot done {ms}", file=sys.stderr, flush=True)
+        passes = passes[args.warmup:]
+        stage_keys = ("grid", "count", "emit", "select", "commit")
+        per_pass = [{**rec[k], **{s + "_ms": mean([p[k].get(s, 0.0) for p in passes]) for s in stage_keys}} for k in range(len(radii))]
+        res["surface"] = {
+            "multipliers": mult, "mean_nn": avg, "radii": radii, "points": n, "normal_radius": nr, "normal_max_nn": nk,
+            "orient_k": ok, "triangles": len(mesh.triangles), "device_ms": ms, "passes": per_pass,
+            "what_is_timed": "device_ms: ball_pivot with its allocations and read-backs (the status and the count per pass, "
+                             "the header per round); passes: HIP events around the stages, the read-back inside the stage it ends",
+            "grid_workspace_bytes": int(CL.N.lib().slg_surface_ws_bytes(CL.N.SURFACE_WS_GRID, n, 0, 0))}
+        if not args.no_cpu:
+            voxel, small = 0.0, pc
+            while len(small) > args.surface_cpu_points:
+                voxel = 1.0 if voxel == 0.0 else voxel * 1.25
+                small = CL.voxel_down_sample(pc, voxel)
+            small = oriented(small, max(nr, 2.5 * voxel))
+            s_avg, s_radii = radii_of(small)
+            (s_mesh, s_rec), s_ms = timed(lambda: MS.ball_pivot(small, s_radii, return_record=True))
+            P, Nrm = small.xyz.cpu().numpy(), small.normals.cpu().numpy()
+            t0 = time.perf_counter()
+            want, w_rec, _ = SR.ball_pivot(P, Nrm, s_radii)
+            cpu_ms = (time.perf_counter() - t0) * 1e3
+            same = {"triangles": bool(np.array_equal(s_mesh.triangles.cpu().numpy(), want)), "record": s_rec == w_rec}
+            res["surface"].update({
+                "cpu_points": len(small), "cpu_voxel": voxel, "cpu_radii": s_radii, "cpu_ms": cpu_ms, "cpu_record": w_rec,
+                "device_ms_at_cpu_points": s_ms, "cpu_what": "tests/surface_ref.py: cKDTree lists, the triples of an anchor "
+                                                             "vectorised in NumPy, the greedy selection in Python",
+                "equal_cpu": same, "speedup_vs_cpu_at_cpu_points": cpu_ms / mean(s_ms)})
+            assert all(same.values()), f"the device and the restatement differ: {same}"
+        if args.surface_only:
+            print(json.dumps(res))
+            return
     if args.mesh:
         from structured_light_for_3d_model_replication_amd import mesh as MS
         depth = int(args.mesh)
