@@ -210,6 +210,26 @@ SURFACE_EXPORTS = {
     "slg_surface_round": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp]),
     "slg_surface_commit": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
 }
+# The banded mesher's table (include/slgpu_band.h, csrc/cloud_band.hip), by the same precedent
+# (DESIGN.md §21).
+BAND_EXPORTS = {
+    "slg_band_ws_bytes": (c_i64, [c_i32, c_i32, c_i64, c_i64]),
+    "slg_band_level": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "slg_band_blocks": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "slg_band_nodes": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "slg_band_splat": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "slg_band_divergence": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "slg_band_prolong": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "slg_band_smooth": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
+    "slg_band_iso": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "slg_band_count": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "slg_band_emit": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64,
+                              c_vp]),
+}
+BAND_MIN_DEPTH, BAND_MAX_DEPTH, BAND_MAX_BASE_DEPTH, BAND_BLOCK = 3, 12, 10, 8     # SLG_BAND_*
+BAND_WS_BLOCKS, BAND_WS_SPLAT, BAND_WS_ISO, BAND_WS_EXTRACT = range(4)            # SLG_BAND_WS_*
+# SLG_BAND_STAT_*: indices into a level header's stats
+BAND_STATS = ("seeded_blocks", "active_blocks", "node_blocks", "band_nodes", "interior_nodes")
 SURFACE_WS_GRID, SURFACE_WS_PASS = 0, 1          # SLG_SURFACE_WS_*
 SURFACE_MAX_NEIGHBOURS, SURFACE_MAX_RADII = 512, 8   # SLG_SURFACE_MAX_NEIGHBOURS, SLG_SURFACE_MAX_RADII
 FILTER_BAD_NEIGHBOURS = 8                        # SLG_FILTER_BAD_NEIGHBOURS (slgpu_surface.h)
@@ -275,10 +295,10 @@ def _load():
         fn = getattr(h, name)
         fn.restype = res
         fn.argtypes = args
-    # The second table: the digest check below vouches that the product library is the build of
-    # sources that hold it (tests/test_surface_host.py looks every name up).  A handle without a
+    # The second and third tables: the digest check below vouches that the product library is the build of
+    # sources that hold them (tests/test_surface_host.py and test_band_host.py look every name up).  A handle without a
     # name gets no prototype, and the first call of that name raises ctypes' AttributeError.
-    for name, (res, args) in SURFACE_EXPORTS.items():
+    for name, (res, args) in (*SURFACE_EXPORTS.items(), *BAND_EXPORTS.items()):
         if hasattr(h, name):
             fn = getattr(h, name)
             fn.restype = res

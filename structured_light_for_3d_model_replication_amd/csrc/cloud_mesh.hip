@@ -16,6 +16,7 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "cloud_grid.h"
+#include "mesh_rules.h"
 
 namespace slgmesh {
 
@@ -24,26 +25,7 @@ using slgcloud::Bump;
 using slgcloud::grid_of;
 using slgcloud::kChunk;
 
-struct MeshHdr {        // 256 bytes at the front of the workspace; mesh.py reads it by these offsets
-  int32_t status;       // SLG_FILTER_BAD_* bits
-  int32_t R;
-  int64_t nV, nT;
-  double origin[3];
-  double h, iso, thr;
-};
-static_assert(sizeof(MeshHdr) <= SLG_MESH_HDR_BYTES, "header");
-static_assert(offsetof(MeshHdr, status) == 0 && offsetof(MeshHdr, R) == 4 && offsetof(MeshHdr, nV) == 8 &&
-              offsetof(MeshHdr, nT) == 16 && offsetof(MeshHdr, origin) == 24 && offsetof(MeshHdr, h) == 48 &&
-              offsetof(MeshHdr, iso) == 56 && offsetof(MeshHdr, thr) == 64, "mesh.py's offsets");
-
-constexpr double kOmega = 6.0 / 7.0;
 constexpr int kMaxDepth = 10;
-// the Kuhn tetrahedra: corner codes (dx + 2 dy + 4 dz) along the six axis-order paths 000 -> 111
-__device__ constexpr int kTetCode[6][4] = {{0, 1, 3, 7}, {0, 1, 5, 7}, {0, 2, 3, 7}, {0, 2, 6, 7}, {0, 4, 5, 7}, {0, 4, 6, 7}};
-__device__ constexpr int kTetOdd[6] = {0, 1, 1, 0, 0, 1};
-// owned edge types +x +y +z +xy +xz +yz +xyz as corner codes, and back
-__device__ constexpr int kEdgeCode[7] = {1, 2, 4, 3, 5, 6, 7};
-__device__ constexpr int kTypeOfCode[8] = {-1, 0, 1, 3, 2, 4, 5, 6};
 
 // ---------------------------------------------------------------- workspace
 // Every stage's regions come from cloud_grid.h's Bump, started behind the header.
@@ -164,21 +146,8 @@ static int bind(const char* who, void* ws, int64_t ws_bytes, size_t need) {
   return SLG_OK;
 }
 
-// ---------------------------------------------------------------- the shared rules
-// u = (p - origin) / h, i = floor(u) clamped to 0 .. R - 1 (also for NaN), t = u - i.
-__device__ inline void cell_rule(double p, double o, double h, int R, int* i, double* t) {
-  const double u = (p - o) / h;
-  double c = floor(u);
-  if (!(c > 0.0)) c = 0.0;
-  if (c > (double)(R - 1)) c = (double)(R - 1);
-  *i = (int)c;
-  *t = u - c;
-}
-// The trilinear weight of corner (dx, dy, dz) of the cell.
-__device__ inline double corner_weight_rule(const double* t, int dx, int dy, int dz) {
-  const double wx = dx ? t[0] : 1.0 - t[0], wy = dy ? t[1] : 1.0 - t[1], wz = dz ? t[2] : 1.0 - t[2];
-  return (wx * wy) * wz;
-}
+// ---------------------------------------------------------------- the rules (cell_rule, the corner weights, the Jacobi update, the
+// tetrahedron cases and the header are mesh_rules.h's, shared with cloud_band.hip)
 // Trilinear value of a node field at p: the 8 corners of p's cell, z outermost, x innermost, from 0.
 __device__ inline double trilinear_rule(const double* __restrict__ fld, const double* p, const MeshHdr* hdr) {
   const int R = hdr->R;
@@ -197,9 +166,6 @@ __device__ inline double trilinear_rule(const double* __restrict__ fld, const do
 __device__ inline double nbr_sum_rule(const double* __restrict__ u, int64_t i, int64_t n1, int64_t n2) {
   return ((((u[i - 1] + u[i + 1]) + u[i - n1]) + u[i + n1]) + u[i - n2]) + u[i + n2];
 }
-__device__ inline double jacobi_rule(double uc, double S, double f, double h2) {
-  return uc + kOmega * ((S - h2 * f) / 6.0 - uc);
-}
 __device__ inline double residual_rule(double uc, double S, double f, double h2) { return f - (S - 6.0 * uc) / h2; }
 // Node i of an n1^3 level -> (x, y, z) and whether it lies on the boundary.
 __device__ inline bool node_xyz(uint32_t i, uint32_t n1, uint32_t* x, uint32_t* y, uint32_t* z) {
@@ -208,41 +174,6 @@ __device__ inline bool node_xyz(uint32_t i, uint32_t n1, uint32_t* x, uint32_t* 
   *z = q / n1;
   *y = q - *z * n1;
   return *x == 0 || *y == 0 || *z == 0 || *x == n1 - 1 || *y == n1 - 1 || *z == n1 - 1;
-}
-// The triangles of a tetrahedron whose inside corners are the bits of m (tests/mesh_ref.py:
-// tet_case): tri[j][e] = (p, q), p < q, local corner numbers of the edge carrying vertex e.
-__device__ inline int tet_case_rule(int m, int odd, int (*tri)[3][2]) {
-  int ins[4], outs[4], ni = 0, no = 0;
-  for (int v = 0; v < 4; ++v) {
-    if ((m >> v) & 1) ins[ni++] = v; else outs[no++] = v;
-  }
-  if (ni == 0 || ni == 4) return 0;
-  int nt;
-  if (ni == 2) {
-    const int A = ins[0], B = ins[1];
-    int C = outs[0], D = outs[1];
-    if (((A > C) + (A > D) + (B > C) + (B > D)) & 1) { const int s = C; C = D; D = s; }
-    const int q[2][3][2] = {{{A, C}, {A, D}, {B, D}}, {{A, C}, {B, D}, {B, C}}};
-    for (int j = 0; j < 2; ++j)
-      for (int e = 0; e < 3; ++e) { tri[j][e][0] = q[j][e][0]; tri[j][e][1] = q[j][e][1]; }
-    nt = 2;
-  } else {
-    const int A = ni == 1 ? ins[0] : outs[0];
-    int o[3], k = 0;
-    for (int v = 0; v < 4; ++v)
-      if (v != A) o[k++] = v;
-    if (A & 1) { const int s = o[1]; o[1] = o[2]; o[2] = s; }
-    if (ni == 3) { const int s = o[1]; o[1] = o[2]; o[2] = s; }
-    for (int e = 0; e < 3; ++e) { tri[0][e][0] = A; tri[0][e][1] = o[e]; }
-    nt = 1;
-  }
-  for (int j = 0; j < nt; ++j) {
-    if (odd)
-      for (int c = 0; c < 2; ++c) { const int s = tri[j][1][c]; tri[j][1][c] = tri[j][2][c]; tri[j][2][c] = s; }
-    for (int e = 0; e < 3; ++e)
-      if (tri[j][e][0] > tri[j][e][1]) { const int s = tri[j][e][0]; tri[j][e][0] = tri[j][e][1]; tri[j][e][1] = s; }
-  }
-  return nt;
 }
 // Workgroup b of n -> the 256 nodes it works on.  The workgroups that share an XCD's L2 (b % 8
 // labels them) take one contiguous slab of the level each, so that a slab's y and z neighbours are
@@ -483,8 +414,6 @@ void iso_final_kernel(MeshHdr* hdr, const double* __restrict__ part, int nb, int
 }
 
 // ---------------------------------------------------------------- marching tetrahedra
-__device__ inline bool inside_rule(double chi, double iso) { return chi < iso; }
-
 // Per node: the 7-bit mask of its crossing owned edges; per cell (the node at its 000 corner): the
 // number of triangles of its six tetrahedra.
 __global__ __launch_bounds__(256)

@@ -20,6 +20,11 @@ Beside the watertight mesher, the surface mesh of ``reconstruct_stl(mode="surfac
 device's own rule (``csrc/cloud_surface.hip``): :func:`ball_pivot`, the empty-ball
 triangles radius by radius, restated in ``tests/surface_ref.py``; parity with Open3D's ball
 pivoting is unpinned.
+
+For depths the dense grid cannot hold, the second watertight rule (``csrc/cloud_band.hip``,
+DESIGN.md §21): :func:`poisson_band`, a dense solve at a base depth and finer levels only in blocks
+of 8^3 cells near the points, depth 3..12, restated in ``tests/band_ref.py``; behind the callers'
+``"poisson_rule": "band"``.
 """
 from __future__ import annotations
 
@@ -795,6 +800,211 @@ def ball_pivot(pc, radii, max_rounds: int = DEFAULT_SURFACE_ROUNDS, return_recor
         triangles = torch.cat(parts) if parts else torch.zeros((0, 3), dtype=torch.int32, device=dev)
     out = TriangleMesh(xyz, triangles)
     return (out, record) if return_record else out
+
+
+# ----------------------------------------------------------------------------- banded cascade
+# The second watertight rule (csrc/cloud_band.hip): a dense solve at a base depth, finer levels only
+# in blocks of 8^3 cells near the points.  Our rule, restated in tests/band_ref.py and equal to it
+# bit for bit; parity with Open3D's octree solver is unpinned.
+BAND_MIN_DEPTH, BAND_MAX_DEPTH, BAND_MAX_BASE_DEPTH = N.BAND_MIN_DEPTH, N.BAND_MAX_DEPTH, N.BAND_MAX_BASE_DEPTH
+# Jacobi sweeps per banded level: 16 bring the mean radial error on the test spheres within 1.053 of
+# the dense solve's at the same depth, 8 within 1.12, 32 within 1.017 (tests/test_band_ref.py)
+DEFAULT_BAND_SWEEPS = 16
+_BAND_HDR = np.dtype([*[(k, _HDR.fields[k][0]) for k in _HDR.names], ("unused", "<f8", 7), ("stats", "<i8", 8),
+                      ("pad", "<u1", 64)])                           # one header is N.MESH_HDR_BYTES: an array of them reads as one
+
+
+def check_band_depth(depth, base_depth=None):
+    """``(depth, base_depth)`` of :func:`poisson_band`: ``3 <= depth <= 12``; ``base_depth`` defaults to
+    ``min(8, depth - 1)`` and lies in ``2 .. min(10, depth - 1)``.  ``ValueError`` otherwise."""
+    depth = int(depth)
+    if not BAND_MIN_DEPTH <= depth <= BAND_MAX_DEPTH:
+        raise ValueError(f"depth must be in {BAND_MIN_DEPTH}..{BAND_MAX_DEPTH} for the banded mesher, not {depth}")
+    base = min(8, depth - 1) if base_depth is None else int(base_depth)
+    if not MIN_DEPTH <= base <= min(BAND_MAX_BASE_DEPTH, depth - 1):
+        raise ValueError(f"base_depth must be in {MIN_DEPTH}..{min(BAND_MAX_BASE_DEPTH, depth - 1)} at depth {depth}, not {base}")
+    return depth, base
+
+
+def _band_ws_bytes(stage: int, R: int = 8, n: int = 0, n_blocks: int = 0) -> int:
+    need = int(N.lib().slg_band_ws_bytes(stage, R, n, n_blocks))
+    if need < 0:
+        CL._raise(-need)
+    return need
+
+
+def _band_table_bytes(depth: int, base: int) -> int:
+    """Headers, seed, active and table of every banded level and the block stage's scratch."""
+    sizes = [((1 << l) // N.BAND_BLOCK + 1) ** 3 for l in range(base + 1, depth + 1)]
+    return sum(256 + 6 * m for m in sizes) + _band_ws_bytes(N.BAND_WS_BLOCKS, 1 << depth)
+
+
+def band_workspace_bytes(record: dict) -> int:
+    """Bytes :func:`poisson_band` holds at most, from a record's ``depth``, ``base_depth``, ``points``
+    and per-level ``node_blocks``: the dense base level (:func:`workspace_bytes`), the block tables of
+    every level, per stored block its id and 512 incident bytes, and the larger of a level's solve
+    (``W``, ``V``, ``f`` and two ``chi``, 56 bytes per stored node, the sort's scratch and the
+    parent's ``chi``) and the finest level's extraction (``W``, ``chi``, the masks, counts and scans)."""
+    depth, base, n = int(record["depth"]), int(record["base_depth"]), int(record["points"])
+    blocks = [int(lv["node_blocks"]) for lv in record["levels"]]
+    fixed = workspace_bytes(base, n) + _band_table_bytes(depth, base) + sum(516 * b for b in blocks)
+    sort = _band_ws_bytes(N.BAND_WS_SPLAT, n=n)
+    solve = max(56 * 512 * b + sort + 8 * 512 * p for b, p in zip(blocks, [0, *blocks]))
+    extract = (16 * 512 * blocks[-1] + _band_ws_bytes(N.BAND_WS_ISO, n=n)
+               + (_band_ws_bytes(N.BAND_WS_EXTRACT, n_blocks=blocks[-1]) if blocks[-1] else 0))
+    return fixed + max(solve, extract)
+
+
+def poisson_band(pc, depth: int = 11, base_depth=None, sweeps: int = DEFAULT_BAND_SWEEPS, scale: float = 1.1,
+                 cycles: int = DEFAULT_CYCLES, return_record: bool = False, stream=None, timings=None,
+                 return_fields: bool = False):
+    """The watertight mesh of an oriented cloud by the banded cascade, for depths the
+    dense grid cannot hold: a :class:`TriangleMesh` with ``densities``.  :func:`poisson_grid`'s solve at
+    ``base_depth`` carries the far field.  Every level ``l`` above it exists only in blocks of 8^3
+    cells: a block is seeded when a point's cell lies in it and active when it or one of its 26
+    neighbours is seeded; a node is a band node when an incident cell is active and interior when all
+    8 are.  The level splats and takes the divergence by §16's rules, starts from
+    ``0.125 * P(chi of l - 1)`` (the splat is not normalised by the cell volume) and runs ``sweeps``
+    Jacobi sweeps in which interior nodes update and every other node keeps its value.  The iso value
+    is §16's on the finest level, and marching tetrahedra run over its active cells only: vertices
+    in ascending (block, local node, edge type), triangles in ascending (block, local cell,
+    tetrahedron, triangle).  Our rule, Open3D parity unpinned; a pure function of the cloud.
+
+    The mesh is closed wherever the iso surface stays inside the band (8 to 16 finest cells from a
+    point); where Poisson would close a hole far from every point it ends at the band's edge in a
+    boundary loop, which is what the density trim of the callers removes from a dense solve
+    (:func:`boundary_loops` counts the open edges, :func:`close_holes` closes short loops).
+
+    With ``return_record`` also a dict: ``depth``, ``base_depth``, ``sweeps``, ``points``, per banded
+    level (``levels``) its ``level``, ``seeded_blocks``, ``active_blocks``, ``node_blocks``,
+    ``band_nodes`` and ``interior_nodes``, and ``workspace_bytes`` (:func:`band_workspace_bytes`).  With
+    ``return_fields`` also a list with one dict per banded level of the device arrays ``table``,
+    ``incident``, ``W``, ``V``, ``f``, ``chi`` (node fields are ``[node_blocks, 8, 8, 8]``) and ``iso``.
+    ``ValueError`` for bad arguments (:func:`check_band_depth`), a cloud without normals, a
+    non-finite coordinate or normal, a box without extent or 2^31 vertices or more; ``MemoryError``,
+    naming the bytes, when the workspace exceeds the device's free memory, before the solve is
+    launched.  ``timings``: a dict that gets the stages' times in ms by HIP events (``grid``,
+    ``blocks`` with its read-back, ``base``, per level ``L<l>_nodes``, ``L<l>_splat``,
+    ``L<l>_divergence``, ``L<l>_prolong``, ``L<l>_sweeps``, then ``iso`` and ``extract``)."""
+    depth, base = check_band_depth(depth, base_depth)
+    if isinstance(sweeps, float) and not sweeps.is_integer() or int(sweeps) < 0:
+        raise ValueError(f"poisson_band: sweeps must be a whole number >= 0, not {sweeps}")
+    sweeps = int(sweeps)
+    if not (float(scale) >= 1.0 and np.isfinite(scale)):
+        raise ValueError(f"scale must be finite and >= 1, not {scale}")
+    if int(cycles) < 0:
+        raise ValueError("cycles must be >= 0")
+    pc = CL.as_point_cloud(pc)
+    if not pc.has_points():
+        raise ValueError("Point cloud is empty.")
+    if not pc.has_normals():
+        raise ValueError("poisson_band: the cloud has no normals (estimate and orient them first)")
+    xyz, nrm = CL._check_xyz(pc.xyz), pc.normals.contiguous()
+    n, dev, Rb = xyz.shape[0], xyz.device, 1 << base
+    lib, ls = N.lib(), list(range(base + 1, depth + 1))
+    u8, f64 = dict(dtype=torch.uint8, device=dev), dict(dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        first = workspace_bytes(base, n) + _band_table_bytes(depth, base)
+        free = int(torch.cuda.mem_get_info(dev)[0])
+        if first > free:
+            raise MemoryError(f"poisson_band: depth {depth} needs {first} bytes for its base level and block tables alone, "
+                              f"the device has {free} free")
+        st = E._stream(stream)
+        ws = torch.empty(workspace_bytes(base, n) - 48 * (Rb + 1) ** 3, **u8)
+        hdrs = torch.empty(256 * len(ls), **u8)
+        hdr = [hdrs[256 * k:256 * (k + 1)] for k in range(len(ls))]
+        bws = torch.empty(_band_ws_bytes(N.BAND_WS_BLOCKS, 1 << depth), **u8)
+        stages = _Stages(timings, stream)
+        stages.mark("start")
+        CL._raise(lib.slg_mesh_grid(E._vp(xyz), n, base, float(scale), E._vp(ws), ws.numel(), st))
+        stages.mark("grid")
+        seed, active, table = [], [], []
+        for k, l in enumerate(ls):
+            m = ((1 << l) // N.BAND_BLOCK + 1) ** 3
+            seed.append(torch.empty(m, **u8))
+            active.append(torch.empty(m, **u8))
+            table.append(torch.empty(m, dtype=torch.int32, device=dev))
+            CL._raise(lib.slg_band_level(E._vp(ws), Rb, 1 << l, E._vp(hdr[k]), st))
+            CL._raise(lib.slg_band_blocks(E._vp(xyz), n, 1 << l, E._vp(hdr[k]), E._vp(seed[k]), E._vp(active[k]),
+                                          E._vp(table[k]), E._vp(bws), bws.numel(), st))
+        H = np.frombuffer(hdrs.cpu().numpy().tobytes(), dtype=_BAND_HDR)       # the first read-back: the counts
+        _check_status(H[0], "poisson_band")
+        del bws
+        stages.mark("blocks")
+        record = dict(depth=depth, base_depth=base, sweeps=sweeps, points=n,
+                      levels=[dict(level=l, **{name: int(H[k]["stats"][i]) for i, name in enumerate(N.BAND_STATS)})
+                              for k, l in enumerate(ls)])
+        nblk = [lv["node_blocks"] for lv in record["levels"]]
+        need = record["workspace_bytes"] = band_workspace_bytes(record)
+        if need > free:
+            raise MemoryError(f"poisson_band: depth {depth} over base {base} needs {need} bytes ({nblk[-1]} stored blocks on "
+                              f"the finest level), the device has {free} free")
+        n1 = Rb + 1
+        W = torch.empty((n1, n1, n1), **f64)
+        V = torch.empty((n1, n1, n1, 3), **f64)
+        f, chi = torch.empty_like(W), torch.empty_like(W)
+        CL._raise(lib.slg_mesh_splat(E._vp(xyz), E._vp(nrm), n, Rb, E._vp(ws), ws.numel(), E._vp(W), E._vp(V), st))
+        CL._raise(lib.slg_mesh_divergence(E._vp(V), Rb, E._vp(ws), E._vp(f), st))
+        CL._raise(lib.slg_mesh_solve(E._vp(f), Rb, int(cycles), E._vp(ws), ws.numel(), E._vp(chi), st))
+        stages.mark("base")
+        del W, V, f
+        sws = torch.empty(_band_ws_bytes(N.BAND_WS_SPLAT, n=n), **u8)
+        parent, fields = (chi, None, 0), []
+        for k, l in enumerate(ls):
+            R, nb, h, tb = 1 << l, nblk[k], E._vp(hdr[k]), E._vp(table[k])
+            ids = torch.empty(nb, dtype=torch.int32, device=dev)
+            inc = torch.empty(nb * 512, **u8)
+            CL._raise(lib.slg_band_nodes(R, h, E._vp(active[k]), tb, nb, E._vp(ids), E._vp(inc), st))
+            stages.mark(f"L{l}_nodes")
+            W, V = torch.empty(nb * 512, **f64), torch.empty(nb * 512 * 3, **f64)
+            CL._raise(lib.slg_band_splat(E._vp(xyz), E._vp(nrm), n, R, h, E._vp(seed[k]), tb, E._vp(ids), E._vp(inc), nb,
+                                         E._vp(sws), sws.numel(), E._vp(W), E._vp(V), st))
+            stages.mark(f"L{l}_splat")
+            f = torch.empty(nb * 512, **f64)
+            CL._raise(lib.slg_band_divergence(E._vp(V), R, h, tb, E._vp(ids), E._vp(inc), nb, E._vp(f), st))
+            stages.mark(f"L{l}_divergence")
+            u, tmp = torch.empty(nb * 512, **f64), torch.empty(nb * 512, **f64)
+            CL._raise(lib.slg_band_prolong(E._vp(parent[0]), E._vp(parent[1]), parent[2], R, h, E._vp(ids), E._vp(inc), nb,
+                                           E._vp(u), st))
+            stages.mark(f"L{l}_prolong")
+            CL._raise(lib.slg_band_smooth(E._vp(f), R, h, tb, E._vp(ids), E._vp(inc), nb, sweeps, E._vp(u), E._vp(tmp), st))
+            stages.mark(f"L{l}_sweeps")
+            chi = tmp if sweeps & 1 else u
+            if return_fields:
+                fields.append(dict(level=l, table=table[k], incident=inc.view(nb, 8, 8, 8), W=W.view(nb, 8, 8, 8),
+                                   V=V.view(nb, 8, 8, 8, 3), f=f.view(nb, 8, 8, 8), chi=chi.view(nb, 8, 8, 8)))
+            parent = (chi, table[k], nb)
+            del V, f, u, tmp
+        R, nb, h, tb = 1 << depth, nblk[-1], E._vp(hdr[-1]), E._vp(table[-1])
+        iws = torch.empty(_band_ws_bytes(N.BAND_WS_ISO, n=n), **u8)
+        CL._raise(lib.slg_band_iso(E._vp(chi), E._vp(xyz), n, R, h, tb, nb, E._vp(iws), iws.numel(), st))
+        stages.mark("iso")
+        ews = torch.empty(_band_ws_bytes(N.BAND_WS_EXTRACT, n_blocks=nb), **u8)
+        CL._raise(lib.slg_band_count(E._vp(chi), R, h, tb, E._vp(ids), E._vp(inc), nb, E._vp(ews), ews.numel(), st))
+        H = np.frombuffer(hdrs.cpu().numpy().tobytes(), dtype=_BAND_HDR)       # the second read-back: nV, nT and the node counts
+        for k in range(len(ls)):
+            _check_status(H[k], "poisson_band")
+            record["levels"][k].update({name: int(H[k]["stats"][i]) for i, name in enumerate(N.BAND_STATS)})
+        nv, nt = int(H[-1]["nV"]), int(H[-1]["nT"])
+        if nv >= 1 << 31:
+            raise ValueError(f"the surface has {nv} vertices: 2^31 or more do not fit int32 triangles")
+        vert = torch.empty((nv, 3), **f64)
+        tris = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+        dens = torch.empty(nv, **f64)
+        if nv or nt:
+            CL._raise(lib.slg_band_emit(E._vp(chi), E._vp(W), R, h, tb, E._vp(ids), E._vp(inc), nb, E._vp(ews), ews.numel(),
+                                        E._vp(vert), nv, E._vp(dens), E._vp(tris), nt, st))
+        stages.mark("extract")
+        stages.close()
+    record.update(vertices=nv, triangles=nt)
+    out = [TriangleMesh(vert, tris, dens)]
+    if return_record:
+        out.append(record)
+    if return_fields:
+        for fl in fields:
+            fl["iso"] = float(H[-1]["iso"])
+        out.append(fields)
+    return out[0] if len(out) == 1 else tuple(out)
 
 
 def check_postprocess(params) -> None:

@@ -687,6 +687,27 @@ class ProcessingLogic:
         return MS.check_depth(depth)
 
     @staticmethod
+    def _check_band_poisson(rule, depth, base_depth=None, band_sweeps=None, width=0.0, linear_fit=False):
+        """The arguments of ``mesh.poisson_band`` when ``rule`` is ``"band"``: the depth in
+        3..12, the reference's message above 16 and the grid's ``width`` / ``linear_fit`` refusal as
+        they are.  ``None`` without the key; any other rule is a ``ValueError``."""
+        from . import mesh as MS
+        if rule is None:
+            return None
+        if rule != "band":
+            raise ValueError(f"unknown poisson_rule {rule!r} (\"band\": mesh.poisson_band)")
+        depth = int(depth)
+        if depth > 16:
+            raise ValueError(f"Depth {depth} is too high! Maximum recommended is 12-14. >16 will freeze your PC.")
+        if float(width) != 0.0 or linear_fit:
+            raise ValueError("width != 0 and linear_fit=True are not implemented on the dense grid")
+        depth, base = MS.check_band_depth(depth, base_depth)
+        sweeps = MS.DEFAULT_BAND_SWEEPS if band_sweeps is None else band_sweeps
+        if isinstance(sweeps, bool) or not isinstance(sweeps, (int, float)) or float(sweeps) != int(sweeps) or int(sweeps) < 0:
+            raise ValueError(f"band_sweeps must be a whole number >= 0, not {band_sweeps!r}")
+        return dict(depth=depth, base_depth=base, sweeps=int(sweeps))
+
+    @staticmethod
     def _surface_multipliers(radii_str):
         """``params["radii"]`` parsed as the reference does (``server/processing.py:720``), and what
         ``mesh.check_radii`` will ask of their multiples of a positive distance, asked here."""
@@ -712,7 +733,11 @@ class ProcessingLogic:
         when the file has none), the centroid or tangent-plane orientation, the optional consistency
         pass, then ``mesh.poisson_grid`` at ``params["depth"]`` (default 10), the 0.02 density
         quantile trim and a binary STL.  The mesher is the dense grid's, so a depth
-        above 10 raises ``ValueError``; ``mode="surface"`` (ball pivoting) raises
+        above 10 raises ``ValueError`` unless ``params["poisson_rule"] == "band"`` asks for
+        ``mesh.poisson_band`` (the banded cascade, depth 3..12, with the optional
+        ``params["base_depth"]`` and ``params["band_sweeps"]``; closed wherever the surface stays within
+        the band around the points, and the trim applies as before; any other rule is a
+        ``ValueError``); ``mode="surface"`` (ball pivoting) raises
         ``NotImplementedError``: Open3D's front stays in the reference.  With
         ``params["surface_rule"] == "empty_ball"`` it runs ``mesh.ball_pivot`` instead (DESIGN.md
         §20: the empty-ball triangles, our rule and not Open3D's front) at the radii
@@ -736,7 +761,9 @@ class ProcessingLogic:
             raise FileNotFoundError(f"Input file not found: {input_path}")
         params = params or {}
         if mode == "watertight":
-            depth = ProcessingLogic._check_grid_poisson(params.get("depth", 10))
+            band = ProcessingLogic._check_band_poisson(params.get("poisson_rule"), params.get("depth", 10),
+                                                       params.get("base_depth"), params.get("band_sweeps"))
+            depth = band["depth"] if band else ProcessingLogic._check_grid_poisson(params.get("depth", 10))
             MS.check_stl_path(output_path)
         elif mode == "surface":
             rule = params.get("surface_rule")
@@ -781,7 +808,7 @@ class ProcessingLogic:
             print(f"[Recon] Normals point cloud saved ({len(pcd)} points).")
         if mode == "watertight":
             print(f"[Recon] Poisson Reconstruction (depth={depth})...")
-            mesh = MS.poisson_grid(pcd, depth=depth)
+            mesh = MS.poisson_band(pcd, **band) if band else MS.poisson_grid(pcd, depth=depth)
             if len(mesh.vertices):
                 mesh = MS.remove_vertices_by_mask(mesh, mesh.densities < MS.quantile(mesh.densities, 0.02))
         else:
@@ -833,17 +860,22 @@ class ProcessingLogic:
     @staticmethod
     def mesh_360(input_path, output_path, depth=10, density_trim=0.01, orientation_mode="tangent", width=0.0,
                  scale=1.1, linear_fit=False, n_threads=-1, normal_radius=0.1, normal_max_nn=30,
-                 save_normals_path=None):
+                 save_normals_path=None, poisson_rule=None, base_depth=None, band_sweeps=None):
         """``server/processing.py:790-860`` on the device: :meth:`estimate_oriented_normals`
         (``"radial"``, or the tangent-plane orientation with its fall-back for any other mode, as
         the reference's ``else``), ``mesh.poisson_grid(depth, scale)``, the ``density_trim`` quantile
         trim when positive, and a binary STL.  ``width != 0`` and ``linear_fit=True`` raise
         ``ValueError`` (not implemented on the grid), as does a depth above 10; ``n_threads`` is
-        ignored."""
+        ignored.  ``poisson_rule="band"`` runs ``mesh.poisson_band(depth, base_depth, band_sweeps,
+        scale)`` instead (depth 3..12); ``base_depth`` or ``band_sweeps`` without it, or any
+        other rule, is a ``ValueError``."""
         from . import mesh as MS
         if not os.path.exists(input_path):
             raise FileNotFoundError(f"Input file not found: {input_path}")
-        depth = ProcessingLogic._check_grid_poisson(depth, width, linear_fit)
+        if poisson_rule is None and (base_depth is not None or band_sweeps is not None):
+            raise ValueError("base_depth and band_sweeps belong to poisson_rule=\"band\"")
+        band = ProcessingLogic._check_band_poisson(poisson_rule, depth, base_depth, band_sweeps, width, linear_fit)
+        depth = band["depth"] if band else ProcessingLogic._check_grid_poisson(depth, width, linear_fit)
         if not (float(scale) >= 1.0):
             raise ValueError(f"scale must be >= 1 on the dense grid, not {scale}")
         MS.check_stl_path(output_path)
@@ -853,7 +885,7 @@ class ProcessingLogic:
             orientation_mode="radial" if orientation_mode == "radial" else "tangent")
         print(f"[360 Mesh] Poisson Reconstruction (depth={depth}, width={width}, scale={scale}, linear={linear_fit}, "
               f"threads={n_threads})...")
-        mesh = MS.poisson_grid(pcd, depth=depth, scale=scale)
+        mesh = MS.poisson_band(pcd, scale=scale, **band) if band else MS.poisson_grid(pcd, depth=depth, scale=scale)
         if density_trim > 0.0 and len(mesh.vertices):
             print(f"[360 Mesh] Trimming low density vertices (threshold={density_trim})...")
             mesh = MS.remove_vertices_by_mask(mesh, mesh.densities < MS.quantile(mesh.densities, density_trim))

@@ -83,6 +83,14 @@ outputs), beside its compulsory traffic.  ``--kernel-stats CSV`` takes a ``rocpr
 --stats`` kernel table of a run of this very command and reports the evaluation kernel's time per
 call and its rate against the model.
 
+``--mesh-band DEPTH [--mesh-base D]`` adds the banded cascadic mesher on the same
+oriented view: ``mesh.poisson_band`` with HIP events around the block tables, the dense base level,
+every banded level's stages (node classification, splat, divergence, prolongation, sweeps), the
+iso value and the extraction; per level the blocks and nodes, and the smoother's rate against its
+byte model (24 B per stored node and sweep); the workspace's bytes, ``V`` / ``T`` and the open
+boundary edges (``mesh.boundary_loops``) before and after the 0.02 trim.  A workspace beyond the free
+memory is reported with the bytes it asked for.  ``--mesh-only`` applies.
+
 ``--surface RADII`` adds the surface mesher: normals of the view at
 ``--surface-normals`` (default radius 1.0 / 30) oriented by the tangent-plane orientation with
 ``--surface-orient`` neighbours, then ``mesh.ball_pivot`` at ``RADII`` (multiples of the mean
@@ -138,7 +146,9 @@ def main():
     ap.add_argument("--orient-cpu-points", type=int, default=20000, help="with --orient: the size the host side runs at")
     ap.add_argument("--orient-only", action="store_true", help="with --orient: leave every other step out")
     ap.add_argument("--mesh", type=int, metavar="DEPTH", help="also time the watertight mesher at this depth")
-    ap.add_argument("--mesh-only", action="store_true", help="with --mesh: leave every other step out")
+    ap.add_argument("--mesh-only", action="store_true", help="with --mesh or --mesh-band: leave every other step out")
+    ap.add_argument("--mesh-band", type=int, metavar="DEPTH", help="also time the banded cascadic mesher at this depth (3..12)")
+    ap.add_argument("--mesh-base", type=int, metavar="D", help="with --mesh-band: the dense base depth (default min(8, DEPTH - 1))")
     ap.add_argument("--post", action="store_true", help="with --mesh: also time adjacency, Taubin smoothing and hole closing")
     ap.add_argument("--post-trim", type=float, default=0.02, help="with --post: the density quantile trimmed before it")
     ap.add_argument("--post-punch", type=int, default=0, metavar="K",
@@ -239,6 +249,57 @@ def main():
                 "equal_cpu": same, "speedup_vs_cpu_at_cpu_points": cpu_ms / mean(s_ms)})
             assert all(same.values()), f"the device and the restatement differ: {same}"
         if args.surface_only:
+            print(json.dumps(res))
+            return
+    if args.mesh_band:
+        from structured_light_for_3d_model_replication_amd import mesh as MS
+        depth, base = MS.check_band_depth(args.mesh_band, args.mesh_base)
+        src = CL.orient_normals_towards(CL.estimate_normals(pc, 5.0, 30), CL.centroid(pc), outward=True)
+        mean = lambda v: sum(v) / len(v)
+        band = {"depth": depth, "base_depth": base, "sweeps": MS.DEFAULT_BAND_SWEEPS, "points": n, "normal_radius": 5.0,
+                "normal_max_nn": 30, "free_bytes": int(torch.cuda.mem_get_info()[0])}
+        stages = []
+
+        def run():
+            t = {}
+            out = MS.poisson_band(src, depth=depth, base_depth=base, return_record=True, timings=t)
+            stages.append(t)
+            return out
+
+        try:
+            (mesh, rec), ms = timed(run)
+        except MemoryError as e:                              # the bytes it asked for are the result
+            band["memory_error"] = str(e)
+            mesh = None
+        if mesh is not None:
+            print(f"[device] poisson_band done {ms}", file=sys.stderr, flush=True)
+            stages = stages[args.warmup:]
+            stage_ms = {k: mean([t[k] for t in stages]) for k in stages[0]}
+            levels = []
+            for lv in rec["levels"]:
+                l, nodes = lv["level"], 512 * lv["node_blocks"]
+                sweeps_ms = stage_ms[f"L{l}_sweeps_ms"]
+                model = 24 * nodes * rec["sweeps"]            # u and f read, u written, per stored node and sweep
+                levels.append({**lv, **{k: stage_ms[f"L{l}_{k}_ms"] for k in ("nodes", "splat", "divergence", "prolong", "sweeps")},
+                               "stored_nodes": nodes, "smooth_model_bytes": model,
+                               "smooth_model_tb_per_s": model / (sweeps_ms * 1e-3) / 1e12 if sweeps_ms > 0 else None})
+            loops, ms_loops = timed(lambda: MS.boundary_loops(mesh, 30))
+            thr = MS.quantile(mesh.densities, 0.02)
+            trimmed = MS.remove_vertices_by_mask(mesh, mesh.densities < thr)
+            band.update({
+                "device_ms": ms, "grid_ms": stage_ms["grid_ms"], "blocks_ms": stage_ms["blocks_ms"], "base_ms": stage_ms["base_ms"],
+                "levels": levels, "iso_ms": stage_ms["iso_ms"], "extract_ms": stage_ms["extract_ms"],
+                "what_is_timed": "device_ms: poisson_band with its allocations and two read-backs; the rest: HIP events; blocks_ms "
+                                 "covers the block tables of every level and the first read-back, extract_ms the count, the second "
+                                 "read-back, the allocation and the emit",
+                "vertices": len(mesh.vertices), "triangles": len(mesh.triangles), "workspace_bytes": rec["workspace_bytes"],
+                "dense_workspace_bytes_same_depth": 48 * ((1 << depth) + 1) ** 3,
+                "open_boundary_edges": loops["boundary_edges"], "boundary_loops": loops, "boundary_loops_ms": mean(ms_loops),
+                "vertices_after_trim": len(trimmed.vertices), "triangles_after_trim": len(trimmed.triangles),
+                "open_boundary_edges_after_trim": MS.boundary_loops(trimmed, 30)["boundary_edges"]})
+            del mesh, trimmed
+        res["mesh_band"] = band
+        if args.mesh_only and not args.mesh:
             print(json.dumps(res))
             return
     if args.mesh:
