@@ -226,6 +226,27 @@ BAND_EXPORTS = {
     "slg_band_emit": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64,
                               c_vp]),
 }
+# The mesh audit's table (include/slgpu_audit.h, csrc/cloud_audit.hip), by the same precedent
+# (DESIGN.md §22).
+AUDIT_EXPORTS = {
+    "slg_audit_ws_bytes": (c_i64, [c_i32, c_i64, c_i64]),
+    "slg_audit_edges": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "slg_audit_components_count": (c_i32, [c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "slg_audit_components_emit": (c_i32, [c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "slg_audit_fans": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "slg_audit_measure": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "slg_audit_keep": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp]),
+    "slg_audit_select": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+}
+AUDIT_WS_AUDIT, AUDIT_WS_MEASURE, AUDIT_WS_SELECT = range(3)                      # SLG_AUDIT_WS_*
+AUDIT_CHUNK = 2048                                                                # SLG_AUDIT_CHUNK
+# SLG_AUDIT_STAT_*: indices into the audit header's stats, in the names of mesh.audit's dict
+AUDIT_STATS = ("edges", "boundary_edges", "manifold_edges", "nonmanifold_edges", "inconsistent_edges",
+               "degenerate_triangles", "duplicate_triangles", "nonmanifold_vertices")
+# SLG_AUDIT_VERTEX_* and SLG_AUDIT_TRIANGLE_*: the bits of vertex_class and triangle_class
+(AUDIT_VERTEX_REFERENCED, AUDIT_VERTEX_BOUNDARY, AUDIT_VERTEX_NONMANIFOLD_EDGE, AUDIT_VERTEX_INCONSISTENT,
+ AUDIT_VERTEX_NONMANIFOLD) = 1, 2, 4, 8, 16
+AUDIT_TRIANGLE_DEGENERATE, AUDIT_TRIANGLE_DUPLICATE = 1, 2
 BAND_MIN_DEPTH, BAND_MAX_DEPTH, BAND_MAX_BASE_DEPTH, BAND_BLOCK = 3, 12, 10, 8     # SLG_BAND_*
 BAND_WS_BLOCKS, BAND_WS_SPLAT, BAND_WS_ISO, BAND_WS_EXTRACT = range(4)            # SLG_BAND_WS_*
 # SLG_BAND_STAT_*: indices into a level header's stats
@@ -295,10 +316,10 @@ def _load():
         fn = getattr(h, name)
         fn.restype = res
         fn.argtypes = args
-    # The second and third tables: the digest check below vouches that the product library is the build of
-    # sources that hold them (tests/test_surface_host.py and test_band_host.py look every name up).  A handle without a
+    # The second, third and fourth tables: the digest check below vouches that the product library is the build of
+    # sources that hold them (tests/test_surface_host.py, test_band_host.py and test_audit_host.py look every name up).  A handle without a
     # name gets no prototype, and the first call of that name raises ctypes' AttributeError.
-    for name, (res, args) in (*SURFACE_EXPORTS.items(), *BAND_EXPORTS.items()):
+    for name, (res, args) in (*SURFACE_EXPORTS.items(), *BAND_EXPORTS.items(), *AUDIT_EXPORTS.items()):
         if hasattr(h, name):
             fn = getattr(h, name)
             fn.restype = res

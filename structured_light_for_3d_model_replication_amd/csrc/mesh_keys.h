@@ -1,8 +1,8 @@
 // mesh_keys.h -- what the mesh connectivity units share (included, never compiled alone):
-// cloud_meshpost.hip (adjacency, smoothing, hole closing) and cloud_decimate.hip
-// (quadric edge collapse in rounds; §19).  A directed pair (src, dst) is the 64-bit key
-// src << 32 | dst; everything about connectivity is a radix sort of such keys, a flag pass, a scan
-// and binary searches in the sorted keys.  The keys are 64-bit, another type than cloud_grid.hip's
+// cloud_meshpost.hip (adjacency, smoothing, hole closing), cloud_decimate.hip
+// (quadric edge collapse in rounds; §19) and cloud_audit.hip (edge classes, components; §22).  A
+// directed pair (src, dst) is the 64-bit key src << 32 | dst; everything about connectivity is a
+// radix sort of such keys, a flag pass, a scan and binary searches in the sorted keys.  The keys are 64-bit, another type than cloud_grid.hip's
 // and cloud_mesh.hip's sorts, so rocPRIM is instantiated in each unit that includes this.
 #pragma once
 #include <rocprim/device/device_radix_sort.hpp>
@@ -72,6 +72,21 @@ static inline int sort_keys(const char* who, const uint64_t* in, uint64_t* out, 
   const hipError_t e = rocprim::radix_sort_keys(nullptr, need, in, out, n, 0u, bits, st);
   if (int rc = fits(who, e, need, tb)) return rc;
   if (rocprim::radix_sort_keys(temp, tb, in, out, n, 0u, bits, st) != hipSuccess)
+    return slg_internal_fail(SLG_ERR_HIP, "%s: radix sort failed", who);
+  return SLG_OK;
+}
+// The same sort carrying a 32-bit value per key (cloud_audit.hip: an edge's position and direction
+// bit).  A radix sort is stable: equal keys keep their values in input order.  rocPRIM's scratch by
+// a closed bound: a second copy of the keys and of the values (12 n) and the lookback states.
+static inline size_t sort_pairs_temp(size_t n) { return 16 * n + (4u << 20); }
+static inline int sort_pairs(const char* who, const uint64_t* in, uint64_t* out, const uint32_t* vin, uint32_t* vout, size_t n,
+                             int64_t V, void* temp, size_t tb, hipStream_t st) {
+  unsigned bits = 32;
+  while (bits < 64 && ((uint64_t)V >> (bits - 32))) ++bits;
+  size_t need = 0;
+  const hipError_t e = rocprim::radix_sort_pairs(nullptr, need, in, out, vin, vout, n, 0u, bits, st);
+  if (int rc = fits(who, e, need, tb)) return rc;
+  if (rocprim::radix_sort_pairs(temp, tb, in, out, vin, vout, n, 0u, bits, st) != hipSuccess)
     return slg_internal_fail(SLG_ERR_HIP, "%s: radix sort failed", who);
   return SLG_OK;
 }

@@ -25,6 +25,11 @@ For depths the dense grid cannot hold, the second watertight rule (``csrc/cloud_
 DESIGN.md §21): :func:`poisson_band`, a dense solve at a base depth and finer levels only in blocks
 of 8^3 cells near the points, depth 3..12, restated in ``tests/band_ref.py``; behind the callers'
 ``"poisson_rule": "band"``.
+
+Last, whether the result can be printed (``csrc/cloud_audit.hip``): :func:`audit`
+(closed, manifold, oriented, components, volume, area; self-intersection is not tested),
+:func:`connected_components`, :func:`keep_largest_components`, :func:`remove_small_components` and
+:func:`clean`, restated in ``tests/audit_ref.py``; parity with Open3D's counterparts is unpinned.
 """
 from __future__ import annotations
 
@@ -1007,8 +1012,269 @@ def poisson_band(pc, depth: int = 11, base_depth=None, sweeps: int = DEFAULT_BAN
     return out[0] if len(out) == 1 else tuple(out)
 
 
+# ----------------------------------------------------------------------------- audit and cleanup
+# Whether a mesh is closed, manifold, oriented and one piece, its volume and area, and the two
+# repairs that follow: keeping the large components, dropping degenerate and duplicated triangles
+# and unreferenced vertices (csrc/cloud_audit.hip).  Our rules, restated in tests/audit_ref.py and
+# equal to it bit for bit; parity with Open3D / MeshLab is unpinned.  Self-intersection is not tested.
+_AUDIT_HDR = np.dtype([("status", "<i4"), ("R", "<i4"), ("nV", "<i8"), ("nT", "<i8"), ("nC", "<i8"), ("largest", "<i8"),
+                       ("best", "<u8"), ("unused", "<f8", 10), ("stats", "<i8", 8)])
+AUDIT_COUNTS = ("vertices", "triangles", "unreferenced_vertices", "degenerate_triangles", "duplicate_triangles", "edges",
+                "boundary_edges", "manifold_edges", "nonmanifold_edges", "inconsistent_edges", "nonmanifold_vertices",
+                "components", "largest_component_triangles")
+AUDIT_VERDICTS = ("closed", "edge_manifold", "vertex_manifold", "oriented", "watertight")
+
+
+def _audit_ws(stage: int, device, nv: int, nt: int) -> torch.Tensor:
+    need = int(N.lib().slg_audit_ws_bytes(stage, nv, nt))
+    if need < 0:
+        CL._raise(-need)
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def _audit_header(ws, what: str):
+    hdr = np.frombuffer(ws[:_AUDIT_HDR.itemsize].cpu().numpy().tobytes(), dtype=_AUDIT_HDR)[0]
+    if int(hdr["status"]) & N.FILTER_BAD_INDEX:
+        raise IndexError(f"{what}: a triangle index lies outside 0 .. V - 1")
+    return hdr
+
+
+def audit_verdict(counts: dict) -> dict:
+    """The booleans of :func:`audit` from its counts: ``closed`` (no boundary edge), ``edge_manifold``
+    (no edge with three triangles or more), ``vertex_manifold`` (no vertex with two fans), ``oriented``
+    (no edge whose two triangles run along it in the same direction) and ``watertight``: all four, no
+    degenerate or duplicate triangle and at least one triangle."""
+    v = dict(closed=counts["boundary_edges"] == 0, edge_manifold=counts["nonmanifold_edges"] == 0,
+             vertex_manifold=counts["nonmanifold_vertices"] == 0, oriented=counts["inconsistent_edges"] == 0)
+    v["watertight"] = (all(v.values()) and counts["degenerate_triangles"] == 0 and counts["duplicate_triangles"] == 0
+                       and counts["triangles"] > 0)
+    return v
+
+
+def _audit(mesh, what, stream, fans=True, measure=True, timings=None):
+    """The steps of the audit: ``(result dict, vertex_class, triangle_class, labels, sizes)``."""
+    vert, tris = _post_mesh(mesh, what)
+    nv, nt, dev = len(vert), len(tris), vert.device
+    res = dict.fromkeys(AUDIT_COUNTS, 0)
+    res.update(vertices=nv, triangles=nt, unreferenced_vertices=nv, signed_volume=0.0, area=0.0)
+    u8, i32 = dict(dtype=torch.uint8, device=dev), dict(dtype=torch.int32, device=dev)
+    if nv == 0 or nt == 0:
+        res.update(audit_verdict(res))
+        return (res, torch.zeros(nv, **u8), torch.zeros(nt, **u8), torch.full((nt,), -1, **i32),
+                torch.zeros(0, dtype=torch.int64, device=dev))
+    lib, st = N.lib(), E._stream(stream)
+    with torch.cuda.device(dev):
+        ws = _audit_ws(N.AUDIT_WS_AUDIT, dev, nv, nt)
+        vclass, tclass = torch.empty(nv, **u8), torch.empty(nt, **u8)
+        labels = torch.empty(nt, **i32)
+        stages = _Stages(timings, stream)
+        stages.mark("start")
+        CL._raise(lib.slg_audit_edges(E._vp(tris), nt, nv, E._vp(ws), ws.numel(), E._vp(vclass), E._vp(tclass), st))
+        stages.mark("edges")
+        CL._raise(lib.slg_audit_components_count(nt, nv, E._vp(ws), ws.numel(), E._vp(tclass), E._vp(labels), st))
+        hdr = _audit_header(ws, what)             # the first read-back: the status and the component count
+        nc = int(hdr["nC"])
+        sizes = torch.empty(nc, dtype=torch.int64, device=dev)
+        if nc:
+            CL._raise(lib.slg_audit_components_emit(nt, nv, E._vp(ws), ws.numel(), E._vp(labels), nc, E._vp(sizes), st))
+        stages.mark("components")
+        if fans:
+            CL._raise(lib.slg_audit_fans(E._vp(tris), nt, nv, E._vp(ws), ws.numel(), E._vp(tclass), E._vp(vclass), st))
+        stages.mark("fans")
+        if measure:
+            mws = _audit_ws(N.AUDIT_WS_MEASURE, dev, nv, nt)
+            out = torch.empty(2, dtype=torch.float64, device=dev)
+            CL._raise(lib.slg_audit_measure(E._vp(vert), nv, E._vp(tris), nt, E._vp(mws), mws.numel(), E._vp(out), st))
+            vol, area = out.cpu().numpy().tolist()
+            res.update(signed_volume=vol, area=area)
+        if nc or fans:
+            hdr = _audit_header(ws, what)         # the second: the largest component and the fan count
+        stages.mark("measure")
+        stages.close()
+    res.update({name: int(hdr["stats"][i]) for i, name in enumerate(N.AUDIT_STATS)})
+    res.update(unreferenced_vertices=nv - int(hdr["nV"]), components=nc, largest_component_triangles=int(hdr["largest"]))
+    res.update(audit_verdict(res))
+    return res, vclass, tclass, labels, sizes
+
+
+def audit(mesh: TriangleMesh, return_arrays: bool = False, stream=None, timings=None) -> dict:
+    """Whether ``mesh`` can be printed, as counts, two measures and a verdict.
+
+    A triangle with two equal indices is degenerate and takes no part in the rest.  Every other
+    triangle gives three undirected edges; an edge with one triangle is a boundary edge, with two a
+    manifold edge, with three or more a non-manifold edge; a manifold edge whose two triangles run
+    along it in the same direction is inconsistent.  Two triangles with the same three indices in any
+    winding are duplicates, the one with the lowest index the original.  Triangles that share an
+    edge are one component (sharing a vertex is not enough); a vertex is non-manifold when its
+    triangles form more than one fan around it (the pinch of two cones, the middle of a bow tie).
+
+    Integer counts: ``vertices``, ``triangles``, ``unreferenced_vertices`` (on no triangle at all),
+    ``degenerate_triangles``, ``duplicate_triangles``, ``edges``, ``boundary_edges``, ``manifold_edges``,
+    ``nonmanifold_edges``, ``inconsistent_edges``, ``nonmanifold_vertices``, ``components``,
+    ``largest_component_triangles``.  Floats: ``signed_volume``, the sum of ``a . (b x c) / 6``
+    (positive for a closed mesh wound outwards), and ``area``, both over the triangles that are not
+    degenerate, in a fixed order of additions.  Booleans (:func:`audit_verdict`): ``closed``,
+    ``edge_manifold``, ``vertex_manifold``, ``oriented`` and ``watertight``.  **Self-intersection is
+    not tested**: a watertight verdict says that the surface is a closed, oriented 2-manifold, not that
+    it bounds a solid without overlaps.
+
+    ``return_arrays`` adds, on the device: ``vertex_class`` uint8 ``[V]`` (bit 1 referenced, 2 on a
+    boundary edge, 4 on a non-manifold edge, 8 on an inconsistent edge, 16 a non-manifold vertex),
+    ``triangle_class`` uint8 ``[T]`` (1 degenerate, 2 duplicate), ``labels`` int32 ``[T]`` (the
+    component, numbered by first triangle; -1 for a degenerate triangle) and ``sizes`` int64 ``[C]``.
+    An empty mesh gives the empty answers without a launch; ``IndexError`` for a triangle index
+    outside ``0 .. V - 1``.  Our rule, Open3D parity (``is_watertight`` and its kin) unpinned.
+    ``timings``: a dict that gets the stages' times in ms by HIP events (``edges``; ``components`` with
+    the first read-back; ``fans``; ``measure`` with its two read-backs)."""
+    res, vclass, tclass, labels, sizes = _audit(mesh, "audit", stream, timings=timings)
+    if return_arrays:
+        res.update(vertex_class=vclass, triangle_class=tclass, labels=labels, sizes=sizes)
+    return res
+
+
+def connected_components(mesh: TriangleMesh, stream=None):
+    """``(labels int32 [T], sizes int64 [C])`` on the device: triangles that share an edge are one
+    component, whatever the edge's multiplicity or winding; a component's label is its rank by first
+    triangle; a degenerate triangle has the label -1.  ``IndexError`` for a bad triangle index."""
+    _, _, _, labels, sizes = _audit(mesh, "connected_components", stream, fans=False, measure=False)
+    return labels, sizes
+
+
+def _select(mesh, vert, tris, keep, drop_unreferenced, what, stream):
+    """The triangles with ``keep`` set and, with ``drop_unreferenced``, only the vertices they use."""
+    nv, nt, dev = len(vert), len(tris), vert.device
+    dens = None if mesh.densities is None else mesh.densities.contiguous()
+    with torch.cuda.device(dev):
+        ws = _audit_ws(N.AUDIT_WS_SELECT, dev, nv, nt)
+        v_out, t_out = torch.empty_like(vert), torch.empty_like(tris)
+        d_out = torch.empty_like(dens) if dens is not None else None
+        CL._raise(N.lib().slg_audit_select(E._vp(vert), E._vp(dens), nv, E._vp(tris), nt, E._vp(keep),
+                                           1 if drop_unreferenced else 0, E._vp(ws), ws.numel(), E._vp(v_out), E._vp(d_out),
+                                           E._vp(t_out), E._stream(stream)))
+        hdr = _audit_header(ws, what)
+    kv, kt = int(hdr["nV"]), int(hdr["nT"])
+    return TriangleMesh(v_out[:kv], t_out[:kt], d_out[:kv] if d_out is not None else None)
+
+
+def _keep_components(mesh, choose, what, return_record, stream):
+    """``choose(sizes ndarray) -> bool table``: the components to keep."""
+    res, _, tclass, labels, sizes = _audit(mesh, what, stream, fans=False, measure=False)
+    vert, tris = _post_mesh(mesh, what)
+    nv, nt, nc, dev = len(vert), len(tris), res["components"], vert.device
+    table = np.ascontiguousarray(choose(sizes.cpu().numpy()), np.uint8) if nc else np.zeros(0, np.uint8)
+    if nc and nv and nt:
+        with torch.cuda.device(dev):
+            keep = torch.empty(nt, dtype=torch.uint8, device=dev)
+            tab = torch.from_numpy(table).to(dev)
+            CL._raise(N.lib().slg_audit_keep(E._vp(tclass), E._vp(labels), nt, E._vp(tab), nc, 0, E._vp(keep),
+                                             E._stream(stream)))
+        out = _select(mesh, vert, tris, keep, True, what, stream)
+    else:
+        out = TriangleMesh(vert[:0].clone(), tris[:0].clone(), None if mesh.densities is None else mesh.densities[:0].clone())
+    rec = dict(components_before=nc, components_after=int(table.sum()), triangles_removed=nt - len(out.triangles),
+               vertices_removed=nv - len(out.vertices))
+    return (out, rec) if return_record else out
+
+
+def keep_largest_components(mesh: TriangleMesh, count: int = 1, return_record: bool = False, stream=None):
+    """A new mesh of the ``count`` components (:func:`connected_components`) with the most triangles,
+    ties going to the lower label: their triangles in input order, the vertices they use in input
+    order, renumbered, ``densities`` carried, ``triangle_normals`` not.  Degenerate triangles are
+    dropped.  With ``return_record`` also a dict: ``components_before``, ``components_after``,
+    ``triangles_removed``, ``vertices_removed``.  ``ValueError`` for ``count < 1``."""
+    if isinstance(count, bool) or isinstance(count, float) and not count.is_integer() or int(count) < 1:
+        raise ValueError(f"keep_largest_components: count must be a whole number >= 1, not {count!r}")
+    count = int(count)
+
+    def choose(sizes):
+        order = np.argsort(-sizes, kind="stable")[:count]          # descending size, ties to the lower label
+        table = np.zeros(len(sizes), np.uint8)
+        table[order] = 1
+        return table
+    return _keep_components(mesh, choose, "keep_largest_components", return_record, stream)
+
+
+def remove_small_components(mesh: TriangleMesh, min_triangles: int, return_record: bool = False, stream=None):
+    """A new mesh of the components with at least ``min_triangles`` triangles, as
+    :func:`keep_largest_components` builds it.  ``ValueError`` for ``min_triangles < 0``."""
+    if (isinstance(min_triangles, bool) or isinstance(min_triangles, float) and not min_triangles.is_integer()
+            or int(min_triangles) < 0):
+        raise ValueError(f"remove_small_components: min_triangles must be a whole number >= 0, not {min_triangles!r}")
+    min_triangles = int(min_triangles)
+    return _keep_components(mesh, lambda sizes: sizes >= min_triangles, "remove_small_components", return_record, stream)
+
+
+def clean(mesh: TriangleMesh, degenerate: bool = True, duplicates: bool = True, unreferenced: bool = True,
+          return_record: bool = False, stream=None):
+    """A new mesh without the degenerate triangles, the duplicated triangles (the original of every
+    class, the one with the lowest index, stays) and the vertices no remaining triangle uses, each
+    as asked for.  Order and ``densities`` are preserved, ``triangle_normals`` is not carried.  With
+    ``return_record`` also a dict: ``degenerate_removed``, ``duplicates_removed``, ``vertices_removed``.
+    ``IndexError`` for a triangle index outside ``0 .. V - 1``."""
+    vert, tris = _post_mesh(mesh, "clean")
+    nv, nt, dev = len(vert), len(tris), vert.device
+    rec = dict(degenerate_removed=0, duplicates_removed=0, vertices_removed=0)
+    dens = mesh.densities
+    if nv == 0 or nt == 0:
+        kv = 0 if unreferenced else nv
+        out = TriangleMesh(vert[:kv].clone(), tris.clone(), None if dens is None else dens[:kv].clone())
+        rec["vertices_removed"] = nv - kv
+        return (out, rec) if return_record else out
+    lib, st = N.lib(), E._stream(stream)
+    bits = (N.AUDIT_TRIANGLE_DEGENERATE if degenerate else 0) | (N.AUDIT_TRIANGLE_DUPLICATE if duplicates else 0)
+    with torch.cuda.device(dev):
+        ws = _audit_ws(N.AUDIT_WS_AUDIT, dev, nv, nt)
+        vclass, tclass = torch.empty(nv, dtype=torch.uint8, device=dev), torch.empty(nt, dtype=torch.uint8, device=dev)
+        keep = torch.empty(nt, dtype=torch.uint8, device=dev)
+        CL._raise(lib.slg_audit_edges(E._vp(tris), nt, nv, E._vp(ws), ws.numel(), E._vp(vclass), E._vp(tclass), st))
+        CL._raise(lib.slg_audit_keep(E._vp(tclass), None, nt, None, 0, bits, E._vp(keep), st))
+        hdr = _audit_header(ws, "clean")
+    out = _select(mesh, vert, tris, keep, unreferenced, "clean", stream)
+    stats = dict(zip(N.AUDIT_STATS, (int(s) for s in hdr["stats"])))
+    rec.update(degenerate_removed=stats["degenerate_triangles"] if degenerate else 0,
+               duplicates_removed=stats["duplicate_triangles"] if duplicates else 0, vertices_removed=nv - len(out.vertices))
+    return (out, rec) if return_record else out
+
+
+def format_audit(a: dict) -> str:
+    """One line of an audit: the counts that say something and the verdict."""
+    parts = [f"{a['vertices']} vertices", f"{a['triangles']} triangles", f"{a['components']} components "
+             f"(largest {a['largest_component_triangles']})", f"{a['boundary_edges']} boundary", f"{a['nonmanifold_edges']} "
+             f"non-manifold and {a['inconsistent_edges']} inconsistent edges", f"{a['nonmanifold_vertices']} non-manifold vertices",
+             f"{a['degenerate_triangles']} degenerate", f"{a['duplicate_triangles']} duplicate", f"{a['unreferenced_vertices']} "
+             f"unreferenced", f"volume {a['signed_volume']:.6g}", f"area {a['area']:.6g}"]
+    missing = ["not " + k.replace("_", "-") for k in AUDIT_VERDICTS[:4] if not a[k]]
+    verdict = "watertight" if a["watertight"] else "not watertight (" + ", ".join(
+        missing or ["degenerate or duplicate triangles, or none at all"]) + ")"
+    return ", ".join(parts) + ": " + verdict + "; self-intersection not tested"
+
+
+_AUDIT_KEYS = ("keep_components", "min_component_faces", "clean", "audit")
+
+
+def _whole(value, least: int, what: str) -> int:
+    try:
+        whole = not isinstance(value, bool) and float(value) == int(value)
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole or int(value) < least:
+        raise ValueError(f"postprocess: {what} must be a whole number >= {least}, not {value!r}")
+    return int(value)
+
+
 def check_postprocess(params) -> None:
     """What :func:`postprocess` takes of the reference's ``meshlab_params``: raises before any launch."""
+    if any(k in params for k in _AUDIT_KEYS):
+        if params.get("backend", "device") != "device":
+            raise ValueError(f"postprocess: {', '.join(k for k in _AUDIT_KEYS if k in params)} belong to \"backend\": \"device\", "
+                             f"not {params.get('backend')!r}")
+        if params.get("keep_components") is not None:
+            _whole(params["keep_components"], 1, "keep_components")
+        if params.get("min_component_faces") is not None:
+            _whole(params["min_component_faces"], 0, "min_component_faces")
+        for k in ("clean", "audit"):
+            if not isinstance(params.get(k, False), (bool, np.bool_)):
+                raise ValueError(f"postprocess: {k} must be True or False, not {params[k]!r}")
     _check_iterations(params.get("smooth_iters", 10), "postprocess")
     if params.get("close_holes"):
         check_hole_size(params.get("close_max_size", 30))
@@ -1023,16 +1289,28 @@ def check_postprocess(params) -> None:
         check_target_faces(params.get("target_faces", DEFAULT_TARGET_FACES), "postprocess")
 
 
-def postprocess(mesh: TriangleMesh, meshlab_params: dict, stream=None) -> TriangleMesh:
+def postprocess(mesh: TriangleMesh, meshlab_params: dict, stream=None, return_record: bool = False):
     """The reference's MeshLab step (``server/processing.py:742-787``) on the device, in its order and
     from its keys: ``smooth_type`` ("laplacian", anything else Taubin) with ``smooth_iters``
     (default 10), then ``close_holes`` with ``close_max_size`` (default 30), then ``simplify`` with
     ``"simplify_rule": "rounds"``: :func:`decimate_quadric` to ``target_faces`` (default 50,000).
     ``simplify`` alone names MeshLab's sequential queue, which is another rule, and raises
     ``NotImplementedError``; any other ``simplify_rule`` is a ``ValueError``.  Our rules on the
-    float64 mesh in memory; MeshLab parity unpinned."""
+    float64 mesh in memory; MeshLab parity unpinned.
+
+    Keys of the device's own (with a ``"backend"`` other than ``"device"`` they are a
+    ``ValueError``): ``"keep_components": k`` (:func:`keep_largest_components`) and / or
+    ``"min_component_faces": n`` (:func:`remove_small_components`, after it) before the smoothing;
+    ``"clean": True`` (:func:`clean`) after the hole closing, whose fill is what can double a face, and
+    before ``simplify``; ``"audit": True`` audits the final mesh (:func:`audit`).  With
+    ``return_record`` the result is ``(mesh, audit dict or None)``.  Without these keys nothing
+    changes."""
     params = dict(meshlab_params or {})
     check_postprocess(params)
+    if params.get("keep_components") is not None:
+        mesh = keep_largest_components(mesh, int(params["keep_components"]), stream=stream)
+    if params.get("min_component_faces") is not None:
+        mesh = remove_small_components(mesh, int(params["min_component_faces"]), stream=stream)
     iters = int(params.get("smooth_iters", 10))
     if str(params.get("smooth_type", "taubin")) == "laplacian":
         mesh = smooth_laplacian(mesh, iters, stream=stream)
@@ -1040,6 +1318,9 @@ def postprocess(mesh: TriangleMesh, meshlab_params: dict, stream=None) -> Triang
         mesh = smooth_taubin(mesh, iters, stream=stream)
     if params.get("close_holes"):
         mesh = close_holes(mesh, int(params.get("close_max_size", 30)), stream=stream)
+    if params.get("clean"):
+        mesh = clean(mesh, stream=stream)
     if params.get("simplify"):
         mesh = decimate_quadric(mesh, int(params.get("target_faces", DEFAULT_TARGET_FACES)), stream=stream)
-    return mesh
+    record = audit(mesh, stream=stream) if params.get("audit") else None
+    return (mesh, record) if return_record else mesh

@@ -754,7 +754,11 @@ class ProcessingLogic:
         50,000) after the hole closing (quadric edge collapse in independent rounds,
         our rule and not MeshLab's sequential queue); ``simplify`` without that key raises
         ``NotImplementedError`` (``server/processing.py:778-781``), any other rule or a bad
-        ``target_faces`` ``ValueError``, all before anything is loaded."""
+        ``target_faces`` ``ValueError``, all before anything is loaded.  The device backend also
+        takes ``"keep_components"``, ``"min_component_faces"``, ``"clean"`` and ``"audit"``
+        (``mesh.postprocess``); with ``"audit": True`` one ``[Mesh] audit: ...`` line
+        gives the final mesh's counts and verdict.  With another backend these keys are a
+        ``ValueError``."""
         from . import cloud as CL
         from . import mesh as MS
         if not os.path.exists(input_path):
@@ -783,6 +787,9 @@ class ProcessingLogic:
         device_post = backend == "device"
         if device_post:
             MS.check_postprocess(meshlab_params)
+        elif backend is not None and any(k in meshlab_params for k in MS._AUDIT_KEYS):
+            raise ValueError("meshlab_params: keep_components, min_component_faces, clean and audit belong to "
+                             "\"backend\": \"device\" (mesh.postprocess)")
         print(f"[Recon] Loading {input_path}...")
         pcd = CL.PointCloud.from_file(input_path)
         if not pcd.has_points():
@@ -827,8 +834,10 @@ class ProcessingLogic:
         ProcessingLogic._write_mesh(mesh, output_path, "Recon")
         if device_post:
             print("[MeshLab] Starting post-processing (device backend)...")
-            mesh = MS.postprocess(mesh, meshlab_params)
+            mesh, audit = MS.postprocess(mesh, meshlab_params, return_record=True)
             ProcessingLogic._write_mesh(mesh, output_path, "MeshLab")
+            if audit is not None:
+                print(f"[Mesh] audit: {MS.format_audit(audit)}")
             print(f"[MeshLab] Post-processing complete. Final: {len(mesh.vertices)} vertices, "
                   f"{len(mesh.triangles)} faces. Saved to {output_path}")
         elif meshlab_params and meshlab_params.get("enabled"):
@@ -860,7 +869,8 @@ class ProcessingLogic:
     @staticmethod
     def mesh_360(input_path, output_path, depth=10, density_trim=0.01, orientation_mode="tangent", width=0.0,
                  scale=1.1, linear_fit=False, n_threads=-1, normal_radius=0.1, normal_max_nn=30,
-                 save_normals_path=None, poisson_rule=None, base_depth=None, band_sweeps=None):
+                 save_normals_path=None, poisson_rule=None, base_depth=None, band_sweeps=None, *, keep_components=None,
+                 audit=False):
         """``server/processing.py:790-860`` on the device: :meth:`estimate_oriented_normals`
         (``"radial"``, or the tangent-plane orientation with its fall-back for any other mode, as
         the reference's ``else``), ``mesh.poisson_grid(depth, scale)``, the ``density_trim`` quantile
@@ -868,7 +878,11 @@ class ProcessingLogic:
         ``ValueError`` (not implemented on the grid), as does a depth above 10; ``n_threads`` is
         ignored.  ``poisson_rule="band"`` runs ``mesh.poisson_band(depth, base_depth, band_sweeps,
         scale)`` instead (depth 3..12); ``base_depth`` or ``band_sweeps`` without it, or any
-        other rule, is a ``ValueError``."""
+        other rule, is a ``ValueError``.  ``keep_components=k`` keeps the ``k`` largest connected
+        components of the trimmed mesh (``mesh.keep_largest_components``: the trim tears scraps off
+        the closure) and ``audit=True`` prints one ``[Mesh] audit: ...`` line with the counts and the
+        verdict of the mesh that is written (``mesh.audit``); a ``keep_components``
+        that is no whole number >= 1 is a ``ValueError``."""
         from . import mesh as MS
         if not os.path.exists(input_path):
             raise FileNotFoundError(f"Input file not found: {input_path}")
@@ -878,6 +892,7 @@ class ProcessingLogic:
         depth = band["depth"] if band else ProcessingLogic._check_grid_poisson(depth, width, linear_fit)
         if not (float(scale) >= 1.0):
             raise ValueError(f"scale must be >= 1 on the dense grid, not {scale}")
+        MS.check_postprocess({k: v for k, v in (("keep_components", keep_components), ("audit", audit)) if v is not None})
         MS.check_stl_path(output_path)
         print(f"[360 Mesh] Loading {input_path}...")
         pcd = ProcessingLogic.estimate_oriented_normals(
@@ -891,7 +906,11 @@ class ProcessingLogic:
             mesh = MS.remove_vertices_by_mask(mesh, mesh.densities < MS.quantile(mesh.densities, density_trim))
         else:
             print("[360 Mesh] Density trim is 0.0 -> Keeping watertight result.")
+        if keep_components is not None:
+            mesh = MS.keep_largest_components(mesh, int(keep_components))
         ProcessingLogic._write_mesh(mesh, output_path, "360 Mesh")
+        if audit:
+            print(f"[Mesh] audit: {MS.format_audit(MS.audit(mesh))}")
 
 
 def batch_views() -> int:

@@ -74,6 +74,10 @@ since the trim of an open view removes nothing and leaves no hole): ``vertex_adj
 that adjacency (20 passes), ``boundary_loops`` and ``close_holes`` at 30 edges.  It reports ``V``,
 ``T``, the mean degree, the loop counts and the smoothing pass's rate against the byte model of a
 pass, ``V (24 (deg + 1) + 4 deg + 16 + 24)`` bytes with ``deg`` the mean row length used.
+``--audit`` (with ``--mesh``) adds ``mesh.audit`` of the meshed view before and after
+the trim and, with ``--post``, after the hole closing and after ``mesh.clean`` of that: the stage times
+(HIP events), the counts, the verdict line, the five largest components, the edges step against its
+byte model, and the times of ``mesh.keep_largest_components`` and ``mesh.clean``.
 ``--decimate TARGET`` (with ``--post``) adds ``mesh.decimate_quadric`` of the
 hole-closed mesh to ``TARGET`` faces: per-call time, rounds, collapses, the stop reason, ``V`` and
 ``T`` in and out, the time of every round, and the byte model of the candidate evaluation summed
@@ -153,6 +157,8 @@ def main():
     ap.add_argument("--post-trim", type=float, default=0.02, help="with --post: the density quantile trimmed before it")
     ap.add_argument("--post-punch", type=int, default=0, metavar="K",
                     help="with --post: also drop every K-th vertex (an open view's trim removes nothing, so this makes the holes)")
+    ap.add_argument("--audit", action="store_true",
+                    help="with --mesh: audit the mesh before and after the trim (and after --post), keep the largest component, clean")
     ap.add_argument("--decimate", type=int, metavar="TARGET", help="with --post: also time decimate_quadric to this many faces")
     ap.add_argument("--kernel-stats", metavar="CSV", help="with --decimate: rocprofv3's kernel stats of a run of this command")
     ap.add_argument("--surface", metavar="RADII", help="also time the surface mesher at these multiples of the mean "
@@ -335,6 +341,43 @@ def main():
             "vertices_after_trim": len(trimmed.vertices), "triangles_after_trim": len(trimmed.triangles),
             "workspace_bytes": MS.workspace_bytes(depth, n),
             "solve_model_bytes": model, "solve_model_tb_per_s": model / (stage_ms["solve_ms"] * 1e-3) / 1e12}
+        def audited(m):
+            """mesh.audit of ``m``: the counts, the mean stage times and the five largest components."""
+            stages_a = []
+
+            def run_a():
+                t = {}
+                a = MS.audit(m, return_arrays=True, timings=t)
+                stages_a.append(t)
+                return a
+
+            a, ms_a = timed(run_a)
+            sizes = a.pop("sizes")
+            for k in ("vertex_class", "triangle_class", "labels"):
+                a.pop(k)
+            nt = max(a["triangles"], 1)
+            out = {"audit": a, "device_ms": ms_a, "line": MS.format_audit(a),
+                   "largest_components": torch.sort(sizes, descending=True)[0][:5].tolist(),
+                   "workspace_bytes": int(CL.N.lib().slg_audit_ws_bytes(CL.N.AUDIT_WS_AUDIT, max(a["vertices"], 1), nt))}
+            for k in stages_a[args.warmup:][0] if a["triangles"] and a["vertices"] else ():
+                out["stage_" + k] = mean([t[k] for t in stages_a[args.warmup:]])
+            if "stage_edges_ms" in out and out["stage_edges_ms"] > 0:          # DESIGN.md §22's byte model of the edges step
+                passes = -(-(32 + int(a["vertices"]).bit_length()) // 8)       # radix passes of 8 bits over the key's bits
+                out["edges_sort_passes_assumed"] = passes
+                out["edges_model_bytes"] = (98 + 72 * passes) * nt
+                out["edges_model_tb_per_s"] = out["edges_model_bytes"] / (out["stage_edges_ms"] * 1e-3) / 1e12
+            print(f"[device] audit: {out['line']}", file=sys.stderr, flush=True)
+            return out
+
+        if args.audit:
+            aud = {"what_is_timed": "device_ms: mesh.audit(return_arrays=True) with its allocations and three read-backs; "
+                                    "stage_*: HIP events (components holds the first read-back, measure the other two)",
+                   "before_trim": audited(mesh), "after_trim": audited(trimmed)}
+            (kept, krec), ms_keep = timed(lambda: MS.keep_largest_components(trimmed, 1, return_record=True))
+            (cleaned, crec), ms_clean = timed(lambda: MS.clean(trimmed, return_record=True))
+            aud.update(keep_largest_ms=ms_keep, keep_largest_record=krec, clean_ms=ms_clean, clean_record=crec)
+            res["mesh_audit"] = aud
+            del kept, cleaned
         if args.post:
             if args.post_trim != 0.02:
                 trimmed = MS.remove_vertices_by_mask(mesh, mesh.densities < MS.quantile(mesh.densities, args.post_trim))
@@ -383,6 +426,12 @@ def main():
                                                               "clone of the vertices), divided by 200",
                 "pass_alone_model_tb_per_s": pass_bytes / (alone_ms * 1e-3) / 1e12,
                 "pass_alone_compulsory_tb_per_s": nv * (48 + 4 * deg + 17) / (alone_ms * 1e-3) / 1e12}
+            if args.audit:
+                res["mesh_audit"]["after_post"] = audited(closed)
+                (cleaned, crec), ms_clean = timed(lambda: MS.clean(closed, return_record=True))
+                res["mesh_audit"].update(clean_after_post_ms=ms_clean, clean_after_post_record=crec,
+                                         after_post_clean=audited(cleaned))
+                del cleaned
             if args.decimate is not None:
                 rounds = []
 
