@@ -238,6 +238,24 @@ AUDIT_EXPORTS = {
     "slg_audit_keep": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp]),
     "slg_audit_select": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
 }
+# The self-intersection test's table (include/slgpu_intersect.h, csrc/cloud_intersect.hip), by the same
+# precedent.
+INTERSECT_EXPORTS = {
+    "slg_isect_ws_bytes": (c_i64, [c_i32, c_i64, c_i64, c_i64]),
+    "slg_isect_boxes": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_dbl, c_vp, c_i64, c_vp]),
+    "slg_isect_entries": (c_i32, [c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp]),
+    "slg_isect_candidates_count": (c_i32, [c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp]),
+    "slg_isect_candidates_emit": (c_i32, [c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp]),
+    "slg_isect_test": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "slg_isect_list": (c_i32, [c_i32, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp]),
+}
+ISECT_WS_BOXES, ISECT_WS_ENTRIES, ISECT_WS_PAIRS, ISECT_WS_LIST = range(4)       # SLG_ISECT_WS_*
+ISECT_SPAN_CAP, ISECT_MAX_CELLS, ISECT_TILE = 64, 1024, 64                       # SLG_ISECT_*
+ISECT_BOUND_HEX = "0x1.c000000000007p-51"                                         # SLG_ISECT_BOUND: (7 + 56 E) E, E = 2^-53
+ISECT_INTERSECTING, ISECT_UNCERTAIN = 1, 2                                        # the bits of a verdict and of a class byte
+# SLG_ISECT_STAT_*: indices into the header's stats, in the names of mesh.self_intersections' dict
+ISECT_STATS = ("adjacent_pairs", "tested_pairs", "intersecting_pairs", "uncertain_pairs", "intersecting_triangles",
+               "uncertain_triangles")
 AUDIT_WS_AUDIT, AUDIT_WS_MEASURE, AUDIT_WS_SELECT = range(3)                      # SLG_AUDIT_WS_*
 AUDIT_CHUNK = 2048                                                                # SLG_AUDIT_CHUNK
 # SLG_AUDIT_STAT_*: indices into the audit header's stats, in the names of mesh.audit's dict
@@ -316,10 +334,11 @@ def _load():
         fn = getattr(h, name)
         fn.restype = res
         fn.argtypes = args
-    # The second, third and fourth tables: the digest check below vouches that the product library is the build of
-    # sources that hold them (tests/test_surface_host.py, test_band_host.py and test_audit_host.py look every name up).  A handle without a
+    # The second to fifth tables: the digest check below vouches that the product library is the build of
+    # sources that hold them (tests/test_surface_host.py, test_band_host.py, test_audit_host.py and test_intersect_host.py look every name up).  A handle without a
     # name gets no prototype, and the first call of that name raises ctypes' AttributeError.
-    for name, (res, args) in (*SURFACE_EXPORTS.items(), *BAND_EXPORTS.items(), *AUDIT_EXPORTS.items()):
+    for name, (res, args) in (*SURFACE_EXPORTS.items(), *BAND_EXPORTS.items(), *AUDIT_EXPORTS.items(),
+                              *INTERSECT_EXPORTS.items()):
         if hasattr(h, name):
             fn = getattr(h, name)
             fn.restype = res

@@ -33,6 +33,7 @@ SRCS = [os.path.join(CSRC, n) for n in ("slgpu.hip", "stats.hip", "ply.hip", "co
                                         "cloud_normals.hip", "cloud_icp.hip", "cloud_feature.hip",
                                         "cloud_ransac.hip", "cloud_plane.hip", "cloud_orient.hip", "cloud_mesh.hip", "cloud_meshpost.hip",
                                         "cloud_decimate.hip", "cloud_surface.hip", "cloud_band.hip", "cloud_audit.hip",
+                                        "cloud_intersect.hip",
                                         "code_object.cpp",
                                         "png_gray.cpp",
                                         "gather.cpp")]
@@ -41,6 +42,7 @@ HDR = os.path.join(ROOT, "include", "slgpu.h")
 HDR_SURFACE = os.path.join(ROOT, "include", "slgpu_surface.h")     # the surface mesher's table (csrc/cloud_surface.hip)
 HDR_BAND = os.path.join(ROOT, "include", "slgpu_band.h")           # the banded mesher's table (csrc/cloud_band.hip)
 HDR_AUDIT = os.path.join(ROOT, "include", "slgpu_audit.h")         # the mesh audit's table (csrc/cloud_audit.hip)
+HDR_INTERSECT = os.path.join(ROOT, "include", "slgpu_intersect.h")   # the self-intersection test's table (csrc/cloud_intersect.hip)
 OUT = os.path.join(PKG, "libslgpu.so")
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -73,9 +75,9 @@ def digest_files(srcs=None) -> list[str]:
     srcs = list(srcs or SRCS)
     beside = {os.path.join(d, n) for d in {os.path.dirname(p) for p in srcs} for n in os.listdir(d)
               if n.endswith(SRC_SUFFIXES)}
-    # by name, as the digest names them; the surface, band and audit tables are included by their units like
+    # by name, as the digest names them; the surface, band, audit and intersect tables are included by their units like
     # the headers beside them, so a copy of one beside copied sources stands for it
-    by_name = {os.path.basename(p): p for p in (HDR_SURFACE, HDR_BAND, HDR_AUDIT, *sorted(beside.union(srcs)))}
+    by_name = {os.path.basename(p): p for p in (HDR_SURFACE, HDR_BAND, HDR_AUDIT, HDR_INTERSECT, *sorted(beside.union(srcs)))}
     return [*(by_name[k] for k in sorted(by_name)), HDR]
 
 

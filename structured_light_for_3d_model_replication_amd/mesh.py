@@ -1115,8 +1115,8 @@ def audit(mesh: TriangleMesh, return_arrays: bool = False, stream=None, timings=
     (positive for a closed mesh wound outwards), and ``area``, both over the triangles that are not
     degenerate, in a fixed order of additions.  Booleans (:func:`audit_verdict`): ``closed``,
     ``edge_manifold``, ``vertex_manifold``, ``oriented`` and ``watertight``.  **Self-intersection is
-    not tested**: a watertight verdict says that the surface is a closed, oriented 2-manifold, not that
-    it bounds a solid without overlaps.
+    not tested** (see :func:`self_intersections`): a watertight verdict says that the surface is a
+    closed, oriented 2-manifold, not that it bounds a solid without overlaps.
 
     ``return_arrays`` adds, on the device: ``vertex_class`` uint8 ``[V]`` (bit 1 referenced, 2 on a
     boundary edge, 4 on a non-manifold edge, 8 on an inconsistent edge, 16 a non-manifold vertex),
@@ -1249,7 +1249,146 @@ def format_audit(a: dict) -> str:
     return ", ".join(parts) + ": " + verdict + "; self-intersection not tested"
 
 
-_AUDIT_KEYS = ("keep_components", "min_component_faces", "clean", "audit")
+# ----------------------------------------------------------------------------- self-intersection
+# Which pairs of triangles cross (csrc/cloud_intersect.hip).  Our rule, restated in
+# tests/intersect_ref.py and equal to it exactly; parity with Open3D's is_self_intersecting is unpinned.
+_ISECT_HDR = np.dtype([("status", "<i4"), ("R", "<i4"), ("entries", "<i8"), ("large", "<i8"), ("part", "<i8"), ("runs", "<i8"),
+                       ("candidates", "<i8"), ("cursor", "<u8"), ("dims", "<i4", 3), ("pad", "<i4"), ("origin", "<f8", 3),
+                       ("cell", "<f8"), ("unused", "<f8", 3), ("stats", "<i8", 8), ("ext", "<u8", 6), ("side_sum", "<i8")])
+INTERSECTION_COUNTS = ("candidate_pairs", "adjacent_pairs", "tested_pairs", "intersecting_pairs", "uncertain_pairs",
+                       "intersecting_triangles", "uncertain_triangles")
+INTERSECTION_GRID = ("cells", "entries", "large_triangles")
+
+
+def _isect_ws(stage: int, device, nv: int, nt: int, items: int = 0) -> torch.Tensor:
+    need = int(N.lib().slg_isect_ws_bytes(stage, nv, nt, items))
+    if need < 0:
+        CL._raise(-need)
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def _isect_header(ws, what: str):
+    hdr = np.frombuffer(ws[:_ISECT_HDR.itemsize].cpu().numpy().tobytes(), dtype=_ISECT_HDR)[0]
+    if int(hdr["status"]) & N.FILTER_BAD_INDEX:
+        raise IndexError(f"{what}: a triangle index lies outside 0 .. V - 1")
+    return hdr
+
+
+def _isect_list(which, nt, nc, pws, count, max_pairs, dev, st):
+    """The int32 ``[count, 2]`` list of the pairs with the verdict bit ``which``, or None above ``max_pairs``."""
+    if count > max_pairs:
+        return None
+    out = torch.empty((count, 2), dtype=torch.int32, device=dev)
+    if count:
+        lws = _isect_ws(N.ISECT_WS_LIST, dev, 1, nt, count)
+        CL._raise(N.lib().slg_isect_list(which, nt, nc, E._vp(pws), pws.numel(), count, E._vp(lws), lws.numel(), E._vp(out), st))
+    return out
+
+
+def self_intersections(mesh: TriangleMesh, return_pairs: bool = False, return_arrays: bool = False, max_pairs: int = 1 << 20,
+                       max_candidates: int = 1 << 28, stream=None, timings=None, _cell: float = 0.0) -> dict:
+    """Which pairs of triangles of ``mesh`` cross (the rule is ``tests/intersect_ref.py``).
+
+    A triangle with two equal indices, or with a coordinate that is not finite, takes part in
+    nothing.  A candidate is a pair ``s < t`` of the others whose closed boxes overlap.  Pairs that share
+    two or three vertex *indices* are adjacent: counted, not tested.  With one shared index the two
+    edges opposite it are tested against the other triangle, with none all six.  An edge pierces a
+    triangle iff its ends lie strictly on opposite sides of the plane and it passes the three edges
+    on one strict side; every sign is one fp64 determinant (Shewchuk's ``orient3dfast``), *certain* when
+    it exceeds his stage-A bound.  A pair is intersecting iff an edge pierces, and uncertain iff no
+    edge test is certainly piercing and one is neither certainly excluded nor certainly piercing.
+
+    Integer counts: ``candidate_pairs``, ``adjacent_pairs``, ``tested_pairs``, ``intersecting_pairs``,
+    ``uncertain_pairs``, ``intersecting_triangles``, ``uncertain_triangles``; the boolean
+    ``intersection_free`` (no intersecting and no uncertain pair); and ``cells``, ``entries``,
+    ``large_triangles``, which describe the uniform grid that found the candidates and are
+    informational: nothing else depends on the grid.  ``return_arrays`` adds ``triangle_class`` uint8
+    ``[T]`` on the device (1 intersecting, 2 uncertain).  ``return_pairs`` adds ``pairs`` and
+    ``uncertain``, int32 ``[K, 2]`` on the device ascending by ``(s, t)``, and ``pairs_truncated``: a list
+    longer than ``max_pairs`` is None.  More than ``max_candidates`` candidates are a ``ValueError`` that
+    names the count, raised before they are stored.
+
+    What the rule leaves out: coplanar overlaps and coincident but unwelded vertices give zeros and
+    show up as uncertain, not as intersecting; a fold across a shared edge is an adjacent pair and is
+    not tested; underflow is outside the bound.  Our rule, Open3D parity (``is_self_intersecting``)
+    unpinned.  An empty mesh gives the empty answer without a launch; ``IndexError`` for a triangle
+    index outside ``0 .. V - 1``.  ``timings``: a dict that gets the stages' times in ms by HIP events
+    (``boxes``, ``entries`` with the sort, ``candidates`` with count, read-back and emit, ``test``, ``lists``)."""
+    what = "self_intersections"
+    vert, tris = _post_mesh(mesh, what)
+    for name, value in (("max_pairs", max_pairs), ("max_candidates", max_candidates)):
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 0:
+            raise ValueError(f"{what}: {name} must be a whole number >= 0, not {value!r}")
+    if isinstance(_cell, bool) or not isinstance(_cell, (int, float)) or not (np.isfinite(_cell) and _cell >= 0.0):
+        raise ValueError(f"{what}: _cell must be a finite number >= 0, not {_cell!r}")
+    nv, nt, dev = len(vert), len(tris), vert.device
+    res = dict.fromkeys((*INTERSECTION_COUNTS, *INTERSECTION_GRID), 0)
+    tclass, nc = None, 0
+    pairs = {N.ISECT_INTERSECTING: None, N.ISECT_UNCERTAIN: None}
+    if nv and nt:
+        lib, st = N.lib(), E._stream(stream)
+        with torch.cuda.device(dev):
+            ws = _isect_ws(N.ISECT_WS_BOXES, dev, nv, nt)
+            stages = _Stages(timings, stream)
+            stages.mark("start")
+            CL._raise(lib.slg_isect_boxes(E._vp(vert), nv, E._vp(tris), nt, float(_cell), E._vp(ws), ws.numel(), st))
+            hdr = _isect_header(ws, what)             # the first read-back: the status, the entries, the large list
+            ne, nl = int(hdr["entries"]), int(hdr["large"])
+            res.update(cells=int(np.prod(hdr["dims"].astype(np.int64))), entries=ne, large_triangles=nl)
+            stages.mark("boxes")
+            ews = None
+            if ne:
+                ews = _isect_ws(N.ISECT_WS_ENTRIES, dev, nv, nt, ne)
+                CL._raise(lib.slg_isect_entries(nt, nv, E._vp(ws), ws.numel(), ne, E._vp(ews), ews.numel(), st))
+            stages.mark("entries")
+            ewb = ews.numel() if ews is not None else 0
+            CL._raise(lib.slg_isect_candidates_count(nt, nv, E._vp(ws), ws.numel(), ne, E._vp(ews), ewb, nl, st))
+            nc = int(_isect_header(ws, what)["candidates"])       # the second: the candidates
+            res["candidate_pairs"] = nc
+            if nc > max_candidates:
+                raise ValueError(f"{what}: {nc} candidate pairs, max_candidates is {max_candidates}")
+            pws = None
+            if nc:
+                pws = _isect_ws(N.ISECT_WS_PAIRS, dev, nv, nt, nc)
+                CL._raise(lib.slg_isect_candidates_emit(nt, nv, E._vp(ws), ws.numel(), ne, E._vp(ews), ewb, nl, nc, E._vp(pws),
+                                                        pws.numel(), st))
+            stages.mark("candidates")
+            if nc:
+                tclass = torch.empty(nt, dtype=torch.uint8, device=dev)
+                CL._raise(lib.slg_isect_test(E._vp(vert), nv, E._vp(tris), nt, E._vp(ws), ws.numel(), nc, E._vp(pws), pws.numel(),
+                                             E._vp(tclass), st))
+                hdr = _isect_header(ws, what)         # the third: the counts
+                res.update({name: int(hdr["stats"][i]) for i, name in enumerate(N.ISECT_STATS)})
+            stages.mark("test")
+            if return_pairs and nc:
+                for which, key in ((N.ISECT_INTERSECTING, "intersecting_pairs"), (N.ISECT_UNCERTAIN, "uncertain_pairs")):
+                    pairs[which] = _isect_list(which, nt, nc, pws, res[key], max_pairs, dev, st)
+            stages.mark("lists")
+            stages.close()
+    res["intersection_free"] = intersection_verdict(res)
+    if return_arrays:
+        res["triangle_class"] = tclass if tclass is not None else torch.zeros(nt, dtype=torch.uint8, device=dev)
+    if return_pairs:
+        for which, name in ((N.ISECT_INTERSECTING, "pairs"), (N.ISECT_UNCERTAIN, "uncertain")):
+            res[name] = pairs[which] if nc else torch.zeros((0, 2), dtype=torch.int32, device=dev)
+        res["pairs_truncated"] = res["intersecting_pairs"] > max_pairs or res["uncertain_pairs"] > max_pairs
+    return res
+
+
+def intersection_verdict(counts: dict) -> bool:
+    """``intersection_free`` of :func:`self_intersections`: no intersecting and no uncertain pair."""
+    return counts["intersecting_pairs"] == 0 and counts["uncertain_pairs"] == 0
+
+
+def format_intersections(r: dict) -> str:
+    """One line of a :func:`self_intersections` record."""
+    verdict = "intersection-free" if r["intersection_free"] else "not intersection-free"
+    return (f"{r['candidate_pairs']} candidate pairs ({r['adjacent_pairs']} adjacent, {r['tested_pairs']} tested), "
+            f"{r['intersecting_pairs']} intersecting and {r['uncertain_pairs']} uncertain pairs on {r['intersecting_triangles']} and "
+            f"{r['uncertain_triangles']} triangles: {verdict}; coplanar overlaps and folds over a shared edge not tested")
+
+
+_AUDIT_KEYS = ("keep_components", "min_component_faces", "clean", "audit", "self_intersections")
 
 
 def _whole(value, least: int, what: str) -> int:
@@ -1272,7 +1411,7 @@ def check_postprocess(params) -> None:
             _whole(params["keep_components"], 1, "keep_components")
         if params.get("min_component_faces") is not None:
             _whole(params["min_component_faces"], 0, "min_component_faces")
-        for k in ("clean", "audit"):
+        for k in ("clean", "audit", "self_intersections"):
             if not isinstance(params.get(k, False), (bool, np.bool_)):
                 raise ValueError(f"postprocess: {k} must be True or False, not {params[k]!r}")
     _check_iterations(params.get("smooth_iters", 10), "postprocess")
@@ -1302,9 +1441,11 @@ def postprocess(mesh: TriangleMesh, meshlab_params: dict, stream=None, return_re
     ``ValueError``): ``"keep_components": k`` (:func:`keep_largest_components`) and / or
     ``"min_component_faces": n`` (:func:`remove_small_components`, after it) before the smoothing;
     ``"clean": True`` (:func:`clean`) after the hole closing, whose fill is what can double a face, and
-    before ``simplify``; ``"audit": True`` audits the final mesh (:func:`audit`).  With
-    ``return_record`` the result is ``(mesh, audit dict or None)``.  Without these keys nothing
-    changes."""
+    before ``simplify``; ``"audit": True`` audits the final mesh (:func:`audit`);
+    ``"self_intersections": True`` tests it for crossing triangles (:func:`self_intersections`,
+    DESIGN.md §23).  With ``return_record`` the result is ``(mesh, audit dict or None)``; the
+    intersection record is the dict's ``"self_intersections"`` (a dict with that key alone without
+    ``"audit"``).  Without these keys nothing changes."""
     params = dict(meshlab_params or {})
     check_postprocess(params)
     if params.get("keep_components") is not None:
@@ -1323,4 +1464,6 @@ def postprocess(mesh: TriangleMesh, meshlab_params: dict, stream=None, return_re
     if params.get("simplify"):
         mesh = decimate_quadric(mesh, int(params.get("target_faces", DEFAULT_TARGET_FACES)), stream=stream)
     record = audit(mesh, stream=stream) if params.get("audit") else None
+    if params.get("self_intersections"):
+        record = {**(record or {}), "self_intersections": self_intersections(mesh, stream=stream)}
     return (mesh, record) if return_record else mesh

@@ -757,8 +757,9 @@ class ProcessingLogic:
         ``target_faces`` ``ValueError``, all before anything is loaded.  The device backend also
         takes ``"keep_components"``, ``"min_component_faces"``, ``"clean"`` and ``"audit"``
         (``mesh.postprocess``); with ``"audit": True`` one ``[Mesh] audit: ...`` line
-        gives the final mesh's counts and verdict.  With another backend these keys are a
-        ``ValueError``."""
+        gives the final mesh's counts and verdict, and with ``"self_intersections": True`` a second
+        ``[Mesh] intersections: ...`` line says which of its triangles cross (``mesh.self_intersections``,
+        DESIGN.md §23).  With another backend these keys are a ``ValueError``."""
         from . import cloud as CL
         from . import mesh as MS
         if not os.path.exists(input_path):
@@ -788,7 +789,7 @@ class ProcessingLogic:
         if device_post:
             MS.check_postprocess(meshlab_params)
         elif backend is not None and any(k in meshlab_params for k in MS._AUDIT_KEYS):
-            raise ValueError("meshlab_params: keep_components, min_component_faces, clean and audit belong to "
+            raise ValueError("meshlab_params: keep_components, min_component_faces, clean, audit and self_intersections belong to "
                              "\"backend\": \"device\" (mesh.postprocess)")
         print(f"[Recon] Loading {input_path}...")
         pcd = CL.PointCloud.from_file(input_path)
@@ -836,8 +837,10 @@ class ProcessingLogic:
             print("[MeshLab] Starting post-processing (device backend)...")
             mesh, audit = MS.postprocess(mesh, meshlab_params, return_record=True)
             ProcessingLogic._write_mesh(mesh, output_path, "MeshLab")
-            if audit is not None:
+            if audit is not None and "watertight" in audit:
                 print(f"[Mesh] audit: {MS.format_audit(audit)}")
+            if audit is not None and "self_intersections" in audit:
+                print(f"[Mesh] intersections: {MS.format_intersections(audit['self_intersections'])}")
             print(f"[MeshLab] Post-processing complete. Final: {len(mesh.vertices)} vertices, "
                   f"{len(mesh.triangles)} faces. Saved to {output_path}")
         elif meshlab_params and meshlab_params.get("enabled"):
@@ -869,8 +872,8 @@ class ProcessingLogic:
     @staticmethod
     def mesh_360(input_path, output_path, depth=10, density_trim=0.01, orientation_mode="tangent", width=0.0,
                  scale=1.1, linear_fit=False, n_threads=-1, normal_radius=0.1, normal_max_nn=30,
-                 save_normals_path=None, poisson_rule=None, base_depth=None, band_sweeps=None, *, keep_components=None,
-                 audit=False):
+                 save_normals_path=None, poisson_rule=None, base_depth=None, band_sweeps=None, *, self_intersections=False,
+                 keep_components=None, audit=False):
         """``server/processing.py:790-860`` on the device: :meth:`estimate_oriented_normals`
         (``"radial"``, or the tangent-plane orientation with its fall-back for any other mode, as
         the reference's ``else``), ``mesh.poisson_grid(depth, scale)``, the ``density_trim`` quantile
@@ -882,7 +885,8 @@ class ProcessingLogic:
         components of the trimmed mesh (``mesh.keep_largest_components``: the trim tears scraps off
         the closure) and ``audit=True`` prints one ``[Mesh] audit: ...`` line with the counts and the
         verdict of the mesh that is written (``mesh.audit``); a ``keep_components``
-        that is no whole number >= 1 is a ``ValueError``."""
+        that is no whole number >= 1 is a ``ValueError``.  ``self_intersections=True`` prints a
+        ``[Mesh] intersections: ...`` line for that mesh (``mesh.self_intersections``)."""
         from . import mesh as MS
         if not os.path.exists(input_path):
             raise FileNotFoundError(f"Input file not found: {input_path}")
@@ -892,7 +896,8 @@ class ProcessingLogic:
         depth = band["depth"] if band else ProcessingLogic._check_grid_poisson(depth, width, linear_fit)
         if not (float(scale) >= 1.0):
             raise ValueError(f"scale must be >= 1 on the dense grid, not {scale}")
-        MS.check_postprocess({k: v for k, v in (("keep_components", keep_components), ("audit", audit)) if v is not None})
+        MS.check_postprocess({k: v for k, v in (("keep_components", keep_components), ("audit", audit),
+                                                  ("self_intersections", self_intersections)) if v is not None})
         MS.check_stl_path(output_path)
         print(f"[360 Mesh] Loading {input_path}...")
         pcd = ProcessingLogic.estimate_oriented_normals(
@@ -911,6 +916,8 @@ class ProcessingLogic:
         ProcessingLogic._write_mesh(mesh, output_path, "360 Mesh")
         if audit:
             print(f"[Mesh] audit: {MS.format_audit(MS.audit(mesh))}")
+        if self_intersections:
+            print(f"[Mesh] intersections: {MS.format_intersections(MS.self_intersections(mesh))}")
 
 
 def batch_views() -> int:

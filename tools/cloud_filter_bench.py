@@ -78,6 +78,11 @@ pass, ``V (24 (deg + 1) + 4 deg + 16 + 24)`` bytes with ``deg`` the mean row len
 the trim and, with ``--post``, after the hole closing and after ``mesh.clean`` of that: the stage times
 (HIP events), the counts, the verdict line, the five largest components, the edges step against its
 byte model, and the times of ``mesh.keep_largest_components`` and ``mesh.clean``.
+``--intersect`` (with ``--mesh`` and ``--post``) adds ``mesh.self_intersections`` of the
+view's mesh, of the punched and hole-closed mesh and, with ``--decimate``, of the decimated mesh: the
+call's time, the stage times by HIP events (``boxes``, ``entries`` with the sort, ``candidates``, ``test``,
+``lists``), every count, the one-line form, and the test kernel's determinant rate, ``tested_pairs x 15
+x 40`` flop over the ``test`` stage, against the 78.6 TFLOP/s vector fp64 peak.
 ``--decimate TARGET`` (with ``--post``) adds ``mesh.decimate_quadric`` of the
 hole-closed mesh to ``TARGET`` faces: per-call time, rounds, collapses, the stop reason, ``V`` and
 ``T`` in and out, the time of every round, and the byte model of the candidate evaluation summed
@@ -159,6 +164,8 @@ def main():
                     help="with --post: also drop every K-th vertex (an open view's trim removes nothing, so this makes the holes)")
     ap.add_argument("--audit", action="store_true",
                     help="with --mesh: audit the mesh before and after the trim (and after --post), keep the largest component, clean")
+    ap.add_argument("--intersect", action="store_true",
+                    help="with --mesh --post: test the view's mesh, the hole-closed mesh and the decimated mesh for crossing triangles")
     ap.add_argument("--decimate", type=int, metavar="TARGET", help="with --post: also time decimate_quadric to this many faces")
     ap.add_argument("--kernel-stats", metavar="CSV", help="with --decimate: rocprofv3's kernel stats of a run of this command")
     ap.add_argument("--surface", metavar="RADII", help="also time the surface mesher at these multiples of the mean "
@@ -369,6 +376,35 @@ def main():
             print(f"[device] audit: {out['line']}", file=sys.stderr, flush=True)
             return out
 
+        def intersected(m):
+            """mesh.self_intersections of ``m``: the counts, the mean stage times, the determinant rate."""
+            stages_i = []
+
+            def run_i():
+                t = {}
+                r = MS.self_intersections(m, return_pairs=True, return_arrays=True, timings=t)
+                stages_i.append(t)
+                return r
+
+            r, ms_i = timed(run_i)
+            for k in ("triangle_class", "pairs", "uncertain"):
+                r.pop(k)
+            out = {"record": r, "device_ms": ms_i, "line": MS.format_intersections(r), "vertices": len(m.vertices),
+                   "triangles": len(m.triangles)}
+            for k in stages_i[args.warmup:][0] if stages_i[args.warmup:] and stages_i[args.warmup:][0] else ():
+                out["stage_" + k] = mean([t[k] for t in stages_i[args.warmup:]])
+            if out.get("stage_test_ms", 0) > 0:                                # DESIGN.md §23's flop model of the test kernel
+                out["test_model_flop"] = r["tested_pairs"] * 15 * 40
+                out["test_model_tflop_per_s"] = out["test_model_flop"] / (out["stage_test_ms"] * 1e-3) / 1e12
+                out["test_fraction_of_78_6_tflop_per_s"] = out["test_model_tflop_per_s"] / 78.6
+            print(f"[device] intersections: {out['line']}", file=sys.stderr, flush=True)
+            return out
+
+        if args.intersect:
+            res["mesh_intersect"] = {"what_is_timed": "device_ms: mesh.self_intersections(return_pairs=True, return_arrays=True) "
+                                                      "with its allocations and three read-backs; stage_*: HIP events (boxes "
+                                                      "holds the first read-back, candidates the second, test the third)",
+                                     "view": intersected(trimmed)}
         if args.audit:
             aud = {"what_is_timed": "device_ms: mesh.audit(return_arrays=True) with its allocations and three read-backs; "
                                     "stage_*: HIP events (components holds the first read-back, measure the other two)",
@@ -432,6 +468,8 @@ def main():
                 res["mesh_audit"].update(clean_after_post_ms=ms_clean, clean_after_post_record=crec,
                                          after_post_clean=audited(cleaned))
                 del cleaned
+            if args.intersect:
+                res["mesh_intersect"]["after_post"] = intersected(closed)
             if args.decimate is not None:
                 rounds = []
 
@@ -465,6 +503,8 @@ def main():
                         dec.update(eval_kernel_ms_per_call=eval_ms, eval_model_tb_per_s=model / (eval_ms * 1e-3) / 1e12,
                                    eval_compulsory_tb_per_s=compulsory / (eval_ms * 1e-3) / 1e12)
                 res["mesh_decimate"] = dec
+                if args.intersect:
+                    res["mesh_intersect"]["after_decimate"] = intersected(small)
                 del small
             del adj, closed
         del mesh, trimmed
